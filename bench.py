@@ -17,8 +17,17 @@ likelihoods + the calPlanck prior.  Synthetic theory of the Planck l_max shape
 per-step collective ("weak" scaling).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--walkers 1024] [--no-lensing]
+                    [--dump-outputs DIR] [--full]
 
-The JSON line also carries, outside the headline value: "convergence" (R-1 vs
+A plain run sets up, warms up, times the K steps and prints one JSON line with
+the headline value and "ms_per_step".  --dump-outputs DIR also writes the
+sampler state the timed steps left (what BatchedMCMC.state() hands a caller:
+P, cur_like, mult, n_accept) as DIR/<name>.npy in float64; the inputs are
+seeded, so two builds can be compared output for output.
+
+With --full the JSON line also carries, outside the headline value: "roofline"
+(a second, HIP-event-timed pass of the same steps), "cpu_baseline" (the
+reference's LogLike on the host cores), "binned_cache", "convergence" (R-1 vs
 wall-clock for the headline workload), "config1_tt" (BASELINE configs[1]:
 plik_lite TT on the reference's fixed best-fit theory, 256 walkers per GPU),
 "config4_fast21" (BASELINE configs[3]
@@ -62,6 +71,13 @@ def parse():
     p.add_argument("--walkers", type=int, default=1024, help="walkers per GPU")
     p.add_argument("--groups", type=int, default=int(os.environ.get("CMBS_GROUPS", "1")),
                    help="walker groups stepped on concurrent streams (cmbs_set_groups)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the sampler state after the timed steps as DIR/<name>.npy (float64)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline timing also run the roofline pass, the CPU baseline and the other "
+                        "legs (binned cache, R-1 vs wall-clock, configs[1]/[3]/[4], dragging); --cpu-seconds, "
+                        "--no-cpu-baseline, --cache-steps and the --*-seconds options size or skip those legs "
+                        "and do nothing without --full")
     p.add_argument("--cpu-seconds", type=float, default=2.0, help="per-round CPU baseline sample (5 rounds)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-lensing", action="store_true", help="plik_lite only (configs[2] minus lensing)")
@@ -771,6 +787,37 @@ def kernel_roofline(kern, avg_ms, W, fused_bytes, lens_bytes):
     return roof
 
 
+def step_roofline(kern, per_gpu, W, fused_bytes, lens_bytes):
+    """The "roofline" entry: the dominant kernel of the profiled pass (kern:
+    name -> (total ms, launches)) against its roof, and the step as a whole at
+    per_gpu evals/s against SURVEY 8(d)'s ceiling."""
+    dom = max(kern, key=lambda k: kern[k][0])
+    avg_ms = {k: (v[0] / v[1] if v[1] else None) for k, v in kern.items()}
+    roof = kernel_roofline(dom, avg_ms[dom], W, fused_bytes, lens_bytes)
+    # the step as a whole against SURVEY 8(d)'s ceiling: evals/s x F / min(P_FP64, AI x BW)
+    ai = FLOPS_EVAL / (BYTES_BIN + 8 * (N_B * N_B + 2479 + N_B) / W)
+    ceil_flops = min(PEAK_FP64_TFLOPS * 1e12, ai * PEAK_HBM_GBS * 1e9)
+    roof["step"] = {"achieved_tflops": per_gpu * FLOPS_EVAL / 1e12, "ceiling_tflops": ceil_flops / 1e12,
+                    "frac": per_gpu * FLOPS_EVAL / ceil_flops,
+                    "note": "per GPU, SURVEY 8(d): F = 766,816 flop/eval, B = 51,320 + 3,030,888 / W bytes/eval "
+                            "(plik_lite only; the lensing likelihood's work is not counted)"}
+    roof["avg_kernel_us"] = {k: (v * 1e3 if v else None) for k, v in avg_ms.items()}
+    roof["traffic"], roof["traffic_source"] = pmc_traffic(dom, W)
+    return roof
+
+
+def dump_outputs(outdir, state, rank, world):
+    """--dump-outputs: the sampler state after the last timed step, as a caller
+    of BatchedMCMC.state() receives it -- every walker's point P [W, num_params],
+    CurLike [W], multiplicity [W] and accept count [W] -- one float64 .npy each
+    (a few tens of KB at 1024 walkers).  With several ranks each writes its own
+    walkers as <name>_rank<r>.npy."""
+    os.makedirs(outdir, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    for name, a in zip(("P", "cur_like", "mult", "n_accept"), state):
+        np.save(os.path.join(outdir, f"{name}{tag}.npy"), np.asarray(a, dtype=np.float64))
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -829,8 +876,10 @@ def main():
         devices = [int(p.item()) for p in parts]
     with tempfile.TemporaryDirectory() as td:
         smp, likes, theory, _ = build_problem(W, rank, td, args.groups, lensing=not args.no_lensing)
-        lens_bytes = lensing_window_bytes(os.path.join(td, "refdata")) if not args.no_lensing else (0, 0)
-        fused_bytes = lensing_window_bytes(os.path.join(td, "refdata"), True) if not args.no_lensing else (0, 0)
+        lens_bytes = fused_bytes = (0, 0)
+        if args.full and not args.no_lensing:
+            lens_bytes = lensing_window_bytes(os.path.join(td, "refdata"))
+            fused_bytes = lensing_window_bytes(os.path.join(td, "refdata"), True)
 
         def barrier():
             if world > 1:
@@ -851,49 +900,45 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         evals = world * W * args.steps
+        final = smp.state()                            # what the timed steps left: P, cur_like, mult, n_accept
+        acc_rate = float(final[3].sum()) / (W * (args.warmup + args.steps))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, final, rank, world)
 
-        # roofline pass: same steps with per-kernel HIP events on the launch stream
-        N.profile_reset()
-        N.profile_enable(True)
-        smp.step(args.steps, fast_only=True)
-        torch.cuda.synchronize()
-        N.profile_enable(False)
-        kern = {k: N.profile_read(k) for k in KERNELS}
-        kern = {k: v for k, v in kern.items() if v[1]}
-        _, _, _, nacc = smp.state()
-        acc_rate = float(nacc.sum()) / (W * (args.warmup + 2 * args.steps))
+        kern = None
+        if args.full:
+            # roofline pass: same steps with per-kernel HIP events on the launch stream
+            N.profile_reset()
+            N.profile_enable(True)
+            smp.step(args.steps, fast_only=True)
+            torch.cuda.synchronize()
+            N.profile_enable(False)
+            kern = {k: N.profile_read(k) for k in KERNELS}
+            kern = {k: v for k, v in kern.items() if v[1]}
+            _, _, _, nacc = smp.state()
+            acc_rate = float(nacc.sum()) / (W * (args.warmup + 2 * args.steps))
         cache = None
-        if args.cache_steps > 0 and not args.no_lensing:
+        if args.full and args.cache_steps > 0 and not args.no_lensing:
             cache = binned_cache_run(smp, W, world, args.cache_steps)
         conv = None
-        if args.converge_seconds > 0:
+        if args.full and args.converge_seconds > 0:
             conv = convergence_run(W, rank, world, td, args.converge_seconds, lensing=not args.no_lensing)
         c1 = None
-        if args.config1_seconds >= 0:
+        if args.full and args.config1_seconds >= 0:
             c1 = config1_run(256, rank, world, td, args.config1_seconds)
         c4 = None
-        if args.config4_seconds >= 0:
+        if args.full and args.config4_seconds >= 0:
             c4 = config4_run(512, rank, world, td, args.config4_seconds)
         c5 = None
-        if args.config5_seconds >= 0:
+        if args.full and args.config5_seconds >= 0:
             c5 = config5_run(W, rank, world, td, args.config5_seconds)
         c2d = None
-        if args.drag_seconds >= 0 and not args.no_lensing:
+        if args.full and args.drag_seconds >= 0 and not args.no_lensing:
             c2d = drag_run(W, rank, world, td, args.drag_seconds)
 
-    dom = max(kern, key=lambda k: kern[k][0])
-    avg_ms = {k: (v[0] / v[1] if v[1] else None) for k, v in kern.items()}
-    roof = kernel_roofline(dom, avg_ms[dom], W, fused_bytes, lens_bytes)
-    # the step as a whole against SURVEY 8(d)'s ceiling: evals/s x F / min(P_FP64, AI x BW)
-    per_gpu = evals / dt / world
-    ai = FLOPS_EVAL / (BYTES_BIN + 8 * (N_B * N_B + 2479 + N_B) / W)
-    ceil_flops = min(PEAK_FP64_TFLOPS * 1e12, ai * PEAK_HBM_GBS * 1e9)
-    roof["step"] = {"achieved_tflops": per_gpu * FLOPS_EVAL / 1e12, "ceiling_tflops": ceil_flops / 1e12,
-                    "frac": per_gpu * FLOPS_EVAL / ceil_flops,
-                    "note": "per GPU, SURVEY 8(d): F = 766,816 flop/eval, B = 51,320 + 3,030,888 / W bytes/eval "
-                            "(plik_lite only; the lensing likelihood's work is not counted)"}
-    roof["avg_kernel_us"] = {k: (v * 1e3 if v else None) for k, v in avg_ms.items()}
-    roof["traffic"], roof["traffic_source"] = pmc_traffic(dom, W)
+    roof = None
+    if kern is not None:
+        roof = step_roofline(kern, evals / dt / world, W, fused_bytes, lens_bytes)
 
     if rank == 0:
         out = {
@@ -912,8 +957,9 @@ def main():
                        "parallelism": f"walkers sharded over {world} rank(s), no per-step collective",
                        "rank_devices": devices, "dist_backend": args.dist_backend if world > 1 else None,
                        "accept_rate": acc_rate},
-            "roofline": roof,
         }
+        if roof is not None:
+            out["roofline"] = roof
         if conv is not None:
             out["convergence"] = conv
         if cache is not None:
@@ -926,7 +972,7 @@ def main():
             out["config5_bk15_plik"] = c5
         if c2d is not None:
             out["config2_drag"] = c2d
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, lensing=not args.no_lensing)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -7,7 +7,7 @@
 set -u
 mkdir -p gpurun_out/ab
 REPS=${REPS:-2}
-ARGS=${BENCH_ARGS:---steps 300 --warmup 20 --no-cpu-baseline --cache-steps -1 --converge-seconds 0 --config1-seconds -1 --config4-seconds -1 --config5-seconds -1 --drag-seconds -1}
+ARGS=${BENCH_ARGS:---steps 300 --warmup 20 --full --no-cpu-baseline --cache-steps -1 --converge-seconds 0 --config1-seconds -1 --config4-seconds -1 --config5-seconds -1 --drag-seconds -1}
 for rep in $(seq 1 $REPS); do
   i=0
   for v in "$@"; do

@@ -5,7 +5,7 @@ set -u
 R="$GRAFT_REPO_ROOT"
 OUT="$R/gpurun_out/calls"
 mkdir -p "$OUT"
-NB="--no-cpu-baseline --converge-seconds 0 --config1-seconds -1 --config4-seconds -1 --config5-seconds -1 --drag-seconds -1"
+NB="--full --no-cpu-baseline --converge-seconds 0 --config1-seconds -1 --config4-seconds -1 --config5-seconds -1 --drag-seconds -1"
 for rep in $(seq 1 ${REPS:-2}); do
   for wu in 5 200; do
     timeout -k 10 300 python3 "$R/bench.py" --gpus 1 --steps 20 --warmup $wu $NB > "$OUT/b_${wu}_$rep.json" 2>/dev/null || exit $?

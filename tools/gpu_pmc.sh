@@ -8,7 +8,7 @@ OUTD=${PMC_OUT:-pmc}
 mkdir -p gpurun_out/$OUTD
 cd /tmp && export TMPDIR=/tmp
 R="$GRAFT_REPO_ROOT"
-B=${PMC_BENCH_ARGS:-"--no-cpu-baseline --steps 60 --warmup 5 --cache-steps -1 --converge-seconds 0 --config1-seconds -1 --config4-seconds -1 --config5-seconds -1 --drag-seconds -1"}
+B=${PMC_BENCH_ARGS:-"--full --no-cpu-baseline --steps 60 --warmup 5 --cache-steps -1 --converge-seconds 0 --config1-seconds -1 --config4-seconds -1 --config5-seconds -1 --drag-seconds -1"}
 pass() {
   name=$1; shift
   timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d "$R/gpurun_out/$OUTD/$name" -o run \
