@@ -3520,13 +3520,20 @@ void sampler_step(cmbs *s, int n_steps, int fast_only, hipStream_t stream) {
     // step chain of every group breadth-first so the queues interleave, join
     HIP_CHECK(hipEventRecord(s->events[MAXGROUPS], stream));
     for (int g = 0; g < G; g++) HIP_CHECK(hipStreamWaitEvent(s->streams[g], s->events[MAXGROUPS], 0));
+    // A fused pair (the window pass over one theory buffer) is evaluated for the
+    // whole walker set after the groups' Metropolis launches, all on the
+    // caller's stream: a group's own loglike_batch splits the window sums
+    // differently from the pass, and a walker's terms must not depend on the
+    // number of groups.
+    const bool whole = s->tpass != nullptr;
     for (int k = 0; k <= n_steps; k++) {
         const HistRow row = k > 0 ? next_hist(s) : HistRow{};
         for (int g = 0; g < G; g++) {
             const int g0 = s->grp0[g], g1 = s->grp0[g + 1];
-            launch_mh(s, k > 0, k < n_steps, fast_only, row, s->streams[g], g0, g1);
-            if (k < n_steps) eval_likes(s, s->streams[g], false, g0, g1, s->ws_g[g].p);
+            launch_mh(s, k > 0, k < n_steps, fast_only, row, whole ? stream : s->streams[g], g0, g1);
+            if (k < n_steps && !whole) eval_likes(s, s->streams[g], false, g0, g1, s->ws_g[g].p);
         }
+        if (k < n_steps && whole) eval_likes(s, stream, false, 0, s->W, s->ws.p);
     }
     for (int g = 0; g < G; g++) {
         HIP_CHECK(hipEventRecord(s->events[g], s->streams[g]));

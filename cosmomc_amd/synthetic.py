@@ -691,13 +691,21 @@ def chain_problem(n: int, seed: int, extra: dict | None = None):
     d = [1.0 / math.sqrt(corr[i][i]) for i in range(n)]
     cov = np.array([[corr[i][j] * d[i] * d[j] * sig[i] * sig[j] for j in range(n)] for i in range(n)])
     center = [g[n * n + n + i] for i in range(n)]
-    pmin = [center[i] - 4.0 * sig[i] for i in range(n)]
-    pmax = [center[i] + 4.0 * sig[i] for i in range(n)]
+    bs = float(extra.get("bound_sigmas", 4.0))
+    pmin = [center[i] - bs * sig[i] for i in range(n)]
+    pmax = [center[i] + bs * sig[i] for i in range(n)]
     pmean = [0.0] * n
     pstd = [0.0] * n
     pmean[-1] = center[-1] + 0.2 * sig[-1]
     pstd[-1] = 2.0 * sig[-1]
     P0 = [center[i] + 0.5 * sig[i] * g[n * n + 2 * n + i] for i in range(n)]
+    if "bound_sigmas" in extra:
+        # tight bounds: halve a start offset until the start lies strictly inside
+        for i in range(n):
+            off = 0.5 * sig[i] * g[n * n + 2 * n + i]
+            while not pmin[i] < center[i] + off < pmax[i]:
+                off = 0.5 * off
+            P0[i] = center[i] + off
     nf = extra.get("fixed", 0)
     fv = [0.3 + 0.1 * k for k in range(nf)]
     center += fv

@@ -137,7 +137,19 @@ CHAIN_CASES = [
      2, 3, 2.4, 0, 300, {"lincomb": 1, "fixed": 2}),
     # dragging with a 21-parameter fast block (interp_steps = 64)
     ("gauss27_fast21_drag", 27, [list(range(1, 7)), list(range(7, 28))], 1, 2, 2.4, 2, 40, {"lincomb": 1}),
+    # tight bounds (extra["bound_sigmas"] in place of 4) and Temperature /= 1 (extra["temperature"]):
+    # a large share of the trials is logZero (rejected without a randexp1 draw, calclike.f90:97-151)
+    # and AddLikeTemp divides the main term and the prior (:82-94).  The gauss6_fast_only layout,
+    ("gauss6_fast_only_tight_T2p5", 6, [[1, 2], [3, 4, 5], [6]], 1, 1, 1.9, 1, 240,
+     {"burn_in": 0, "bound_sigmas": 1.5, "temperature": 2.5}),
+    # the gauss3_n1_blocks layout (full GetProposal cycle),
+    ("gauss3_n1_blocks_tight_T0p5", 3, [[1], [2], [3]], 1, 3, 2.4, 0, 240,
+     {"burn_in": 5, "bound_sigmas": 1.5, "temperature": 0.5}),
+    # and the gauss6_drag layout (drags aborted at an out-of-bounds end point)
+    ("gauss6_drag_tight_T2", 6, [[1, 2], [3, 4, 5], [6]], 1, 2, 2.4, 2, 240,
+     {"bound_sigmas": 1.5, "temperature": 2.0}),
 ]
+LOGZERO = 1e30                      # settings.f90: logZero
 
 
 def chain_problem(n: int, seed: int, extra=None):
@@ -181,7 +193,7 @@ def gen_rng():
             cov, center, pmin, pmax, pmean, pstd, P0, lin = prob
             npar = len(center)
             ij, kl = 4321 + ci, 9373
-            T = 1.0
+            T = float(extra.get("temperature", 1.0))
             incl = int(extra.get("include_fixed", 0))
             burn = int(extra.get("burn_in", 2))
             used = list(range(1, n + 1))
@@ -219,6 +231,18 @@ def gen_rng():
                                     "mult": pts[:, 0].astype(int).tolist() if pts.size else [],
                                     "thin_fac": int(pts[0, 1]) if pts.size else None},
                 "num_accept": int(mx[0]), "max_like": float(mx[1])}
+            if "bound_sigmas" in extra:
+                # the shape the chain was made for, counted over every step (not only the stored ones):
+                # logZero trials (dragging has no per-step trial value), accepts, and accepts on the
+                # step right after a logZero trial
+                acc = rows[:, 0] != 0
+                out["chains"][name]["n_accept"] = int(acc.sum())
+                if fast_only != 2:
+                    lz = rows[:, 1] == LOGZERO
+                    out["chains"][name]["n_logzero"] = int(lz.sum())
+                    out["chains"][name]["n_accept_after_logzero"] = int(np.sum(lz[:-1] & acc[1:]))
+                print(f"  tight bounds: {out['chains'][name].get('n_logzero')} logZero trials of {steps}, "
+                      f"{int(acc.sum())} accepts, {out['chains'][name].get('n_accept_after_logzero')} after logZero")
             nrows = chain_txt.count(b"\n")
             print(f"chain {name:26s} accept rate {rows[:, 0].mean():.3f}  final -lnL {rows[-1, 2]:.6f}  "
                   f"chain rows {nrows}")

@@ -95,7 +95,9 @@ def _oracle_history(ch):
 
 CHAIN_FILE_CASES = ["gauss6_single_block", "gauss6_blocked", "gauss6_fast_only", "gauss3_n1_blocks", "gauss6_drag",
                     "gauss4_drag_every_step", "gauss27_fast21_fast_only", "gauss27_fast21_os3",
-                    "gauss27_fast12_9_lincomb", "gauss40_slow_fast", "gauss27_fast21_drag"]
+                    "gauss27_fast12_9_lincomb", "gauss40_slow_fast", "gauss27_fast21_drag",
+                    # Temperature /= 1 (the like column carries it) and tight bounds
+                    "gauss6_fast_only_tight_T2p5", "gauss3_n1_blocks_tight_T0p5", "gauss6_drag_tight_T2"]
 
 
 @pytest.mark.parametrize("name", CHAIN_FILE_CASES)

@@ -31,7 +31,8 @@ def _same_state(a, b):
         np.testing.assert_array_equal(x, y)
 
 
-@pytest.mark.parametrize("name", ["gauss6_blocked", "gauss6_fast_only", "gauss3_n1_blocks"])
+@pytest.mark.parametrize("name", ["gauss6_blocked", "gauss6_fast_only", "gauss3_n1_blocks",
+                                  "gauss3_n1_blocks_tight_T0p5"])    # checkpoint taken among logZero rejections
 def test_resume_continues_chains_exactly(rng_golden, tmp_path, name):
     from cosmomc_amd.checkpoint import read_checkpoint, write_checkpoint
     ch = rng_golden["chains"][name]

@@ -17,7 +17,9 @@ from cosmomc_amd import synthetic as syn
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-CHAINS = ["gauss6_single_block", "gauss6_blocked", "gauss6_fast_only", "gauss3_n1_blocks"]
+CHAINS = ["gauss6_single_block", "gauss6_blocked", "gauss6_fast_only", "gauss3_n1_blocks",
+          # bounds at 1.5 sigma (about half the trials logZero) and Temperature 2.5 / 0.5
+          "gauss6_fast_only_tight_T2p5", "gauss3_n1_blocks_tight_T0p5"]
 # BASELINE configs[3] shapes: 21-parameter fast blocks (rotations read in place from HBM when the
 # LDS image is full), a 12 + 9 split, 40 used parameters, fixed parameters and linear-combination priors
 WIDE_CHAINS = ["gauss27_fast21_fast_only", "gauss27_fast21_os3", "gauss27_fast12_9_lincomb", "gauss40_slow_fast"]
@@ -56,6 +58,84 @@ def _oracle_chain(ch, ij, kl, steps):
     return np.array(Ps), np.array(likes)
 
 
+LOGZERO = 1e30
+TIGHT_CAL = (0.997, 1.004)          # calPlanck bounds, asymmetric round the start 1.0 (proposal step 0.0048)
+TIGHT_A = (0.998, 1.003)            # bounds of the slow amplitude A (proposal steps 0.005 - 0.007)
+
+
+def _oracle_steps(h, t, r, P0, steps, fast_only):
+    """`steps` orc_mh_step calls from P0: per step the accept decision, the
+    point and CurLike after it, and the trial's -lnL (LOGZERO: out of bounds,
+    rejected without a randexp1 draw)."""
+    Q = np.array(P0, dtype=np.float64)
+    cur = C.c_double(po.lib().orc_target_loglike(C.byref(t), Q))
+    tl = C.c_double(0.0)
+    acc, Ps, curs, trials = [], [], [], []
+    for _ in range(steps):
+        acc.append(bool(po.lib().orc_mh_step(h, C.byref(r.s), C.byref(t), Q, C.byref(cur), fast_only, C.byref(tl))))
+        Ps.append(Q.copy())
+        curs.append(cur.value)
+        trials.append(tl.value)
+    return np.array(acc), np.array(Ps), np.array(curs), np.array(trials)
+
+
+def _cal_oracle_chain(orc_plik, dlw, pmin, pmax, pm, ps, T, ij, kl, steps, P0, extra_like=None):
+    """The C oracle's FastParameterSample chain of one walker whose only
+    varying parameter is calPlanck = P(2) (proposal covariance 0.002^2, scale
+    2.4): plik_lite on the walker's theory dlw, `extra_like(user, P)` as the
+    next likelihood of the list, the priors, everything over Temperature T."""
+    h = po.lib().orc_proposer_create(1, np.array([1], dtype=np.int32), np.array([1], dtype=np.int32), 0, 1, 2.4, 1,
+                                     np.array([2], dtype=np.int32))
+    po.lib().orc_proposer_set_covariance(h, np.array([0.002 ** 2]))
+    keep = [np.ascontiguousarray(a, dtype=np.float64) for a in (pmin, pmax, pm, ps)]
+    dlw = np.ascontiguousarray(dlw)
+    t = po.Target()
+    t.num_params = len(P0)
+    t.pmin, t.pmax, t.prior_mean, t.prior_std = [a.ctypes.data for a in keep]
+    t.temperature = T
+    t.plik, t.plik_nuis_index, t.plik_dl, t.plik_ld_field = orc_plik.h, 2, dlw.ctypes.data, dlw.shape[1]
+    cb = None
+    if extra_like is not None:
+        cb = po.EXTRA_LIKE_FN(extra_like)
+        t.extra_like = C.cast(cb, C.c_void_p)
+    out = _oracle_steps(h, t, po.Ranmar(ij, kl), P0, steps, 1)
+    po.lib().orc_proposer_free(h)
+    return out
+
+
+def _edge_counts(acc, trials):
+    """(out-of-bounds trials, accepts, in-bounds rejections, accepts on the
+    step right after an out-of-bounds trial) of an oracle chain."""
+    oob = trials == LOGZERO
+    return int(oob.sum()), int(acc.sum()), int(np.sum(~oob & ~acc)), int(np.sum(oob[:-1] & acc[1:]))
+
+
+def _assert_visits_edges(acc, trials, what):
+    """The oracle chain itself goes to the bounds: 25-75 % of its trials are
+    out of bounds, with at least 3 accepts, 3 in-bounds rejections and one
+    accept directly after an out-of-bounds trial."""
+    n_oob, n_acc, n_rej, n_after = _edge_counts(acc, trials)
+    print(f"{what}: {n_oob} of {len(acc)} trials out of bounds, {n_acc} accepts, {n_rej} in-bounds rejections, "
+          f"{n_after} accepts right after an out-of-bounds trial")
+    assert 0.25 * len(acc) <= n_oob <= 0.75 * len(acc), (what, n_oob)
+    assert n_acc >= 3 and n_rej >= 3 and n_after >= 1, (what, n_acc, n_rej, n_after)
+
+
+def _assert_follows(acc, Ps, curs, rows, P0, w, what, rtol=1e-11, atol=0.0):
+    """History rows [steps, n_used + 1, W] of walker w follow an oracle chain
+    step by step: every accept decision, the point after every step (rtol) and
+    CurLike (rel 1e-9).  A decision may differ legitimately only when randexp1
+    falls within about 1e-8 of like - cur, so none is excused here."""
+    n = rows.shape[1] - 1
+    prev = np.asarray(P0, dtype=np.float64)
+    for k in range(len(acc)):
+        moved = not np.array_equal(rows[k, :n, w], prev)
+        assert moved == bool(acc[k]), f"{what}: accept decision of walker {w} at step {k}"
+        np.testing.assert_allclose(rows[k, :n, w], Ps[k], rtol=rtol, atol=atol, err_msg=f"{what}: walker {w} step {k}")
+        assert rows[k, n, w] == pytest.approx(curs[k], rel=1e-9), (what, w, k)
+        prev = rows[k, :n, w]
+
+
 @pytest.mark.parametrize("name", CHAINS + WIDE_CHAINS)
 def test_walker0_follows_reference_chain(rng_golden, name):
     ch = rng_golden["chains"][name]
@@ -75,7 +155,7 @@ def test_walker0_follows_reference_chain(rng_golden, name):
     assert int(nacc[0]) <= int(sum(ch["accept"]))
 
 
-@pytest.mark.parametrize("name", ["gauss6_blocked", "gauss3_n1_blocks"])
+@pytest.mark.parametrize("name", ["gauss6_blocked", "gauss3_n1_blocks", "gauss6_fast_only_tight_T2p5"])
 def test_all_walkers_vs_oracle(rng_golden, name):
     from cosmomc_amd.sampler import walker_seed
     ch = rng_golden["chains"][name]
@@ -107,7 +187,7 @@ def test_wide_chains_many_walkers_vs_oracle(rng_golden, name):
         assert like[w] == pytest.approx(likes[-1], rel=1e-9)
 
 
-@pytest.mark.parametrize("case", ["TTTEEE_per_walker", "TT_configs1"])
+@pytest.mark.parametrize("case", ["TTTEEE_per_walker", "TT_configs1", "TTTEEE_tight_T0p5"])
 def test_plik_fast_chain_vs_oracle(tmp_path, case):
     """Fast-only Metropolis on calPlanck with native plik_lite + the calPlanck
     prior (batch2/planck_calibration.ini): TTTEEE on per-walker cached theory
@@ -115,14 +195,26 @@ def test_plik_fast_chain_vs_oracle(tmp_path, case):
     (batch2/plik_lite_TT.ini) on one fixed theory (the reference's
     base_plikHM best fit, ld_walker = 0) for 256 walkers.  The one fast
     parameter takes the lean chain (mhlean.h); checked walkers follow the C
-    oracle's chain step by step."""
+    oracle's chain step by step.
+
+    TTTEEE_tight_T0p5: plik alone on the default schedule (mh_bin_kernel), 130
+    walkers (two tiles and a tail of 2), calPlanck bounded to TIGHT_CAL and
+    Temperature 0.5, seeds (59, 70).  The oracle chains of walkers 0, 63, 64
+    and 129 have 26, 28, 30 and 35 of their 60 trials out of bounds, 9, 7, 10
+    and 4 accepts, 25, 25, 20 and 21 in-bounds rejections and 2, 5, 4 and 2
+    accepts right after an out-of-bounds trial; the test asserts that shape
+    (_assert_visits_edges) before comparing.  (num_accept leaves out an accept
+    from mult = 0, MCMC.f90 MoveDone; with these seeds every walker of the
+    oracle still counts at least 2.)"""
     from cosmomc_amd.likelihood import NativeCMBLikelihood
     from cosmomc_amd.sampler import BatchedMCMC, walker_seed
     data = syn.make_plik_lite(12345)
     tt = case == "TT_configs1"
+    tight = case == "TTTEEE_tight_T0p5"
     like = NativeCMBLikelihood("PLIK_LITE", data.write(str(tmp_path), use_cl="TT" if tt else "TT TE EE"))
     like.nuisance_indices = [2]
-    W, steps = (256, 40) if tt else (96, 60)
+    W, steps = (256, 40) if tt else (130, 60) if tight else (96, 60)
+    T = 0.5 if tight else 1.0
     if tt:
         base = syn.base_theory()[:3]
         th = np.broadcast_to(base, (W,) + base.shape)
@@ -131,12 +223,15 @@ def test_plik_fast_chain_vs_oracle(tmp_path, case):
         th = syn.walker_theory(W, seed=3, n_fields=3)
         dl = torch.tensor(th, device="cuda")
     np_ = 3
+    lo, hi = TIGHT_CAL if tight else (0.9, 1.1)
     P0 = np.array([0.0222, 1.0, 3.05])
-    pmin = np.array([0.0222, 0.9, 3.05])
-    pmax = np.array([0.0222, 1.1, 3.05])
+    pmin = np.array([0.0222, lo, 3.05])
+    pmax = np.array([0.0222, hi, 3.05])
     pm = np.array([0.0, 1.0, 0.0])
     ps = np.array([0.0, 0.0025, 0.0])
-    s = BatchedMCMC(W, np_, [2], [[1]], 0, pmin, pmax, pm, ps, propose_scale=2.4, seed_ij=55, seed_kl=66)
+    seeds = (59, 70) if tight else (55, 66)
+    s = BatchedMCMC(W, np_, [2], [[1]], 0, pmin, pmax, pm, ps, propose_scale=2.4, temperature=T, seed_ij=seeds[0],
+                    seed_kl=seeds[1])
     s.set_covariance(np.array([[0.002 ** 2]]))
     s.add_likelihood(like, dl)
     s.set_start(np.tile(P0, (W, 1)))
@@ -144,27 +239,13 @@ def test_plik_fast_chain_vs_oracle(tmp_path, case):
     P, lk, _, nacc = s.state()
     assert np.all(nacc > 0)
     orc = po.PlikLite(data, "TT" if tt else "TT TE EE")
-    for w in ((0, 127, 128, 255) if tt else (0, 5, 64, 95)):
-        ij, kl = walker_seed(55, 66, w)
-        bn = np.array([1], dtype=np.int32)
-        h = po.lib().orc_proposer_create(1, bn, np.array([1], dtype=np.int32), 0, 1, 2.4, 1,
-                                         np.array([2], dtype=np.int32))
-        po.lib().orc_proposer_set_covariance(h, np.array([0.002 ** 2]))
-        t = po.Target()
-        keep = [np.ascontiguousarray(a) for a in (pmin, pmax, pm, ps)]
-        dlw = np.ascontiguousarray(th[w])
-        t.num_params = np_
-        t.pmin, t.pmax, t.prior_mean, t.prior_std = [a.ctypes.data for a in keep]
-        t.temperature = 1.0
-        t.plik, t.plik_nuis_index, t.plik_dl, t.plik_ld_field = orc.h, 2, dlw.ctypes.data, dlw.shape[1]
-        r = po.Ranmar(ij, kl)
-        Q = P0.copy()
-        cur = C.c_double(po.lib().orc_target_loglike(C.byref(t), Q))
-        for _ in range(steps):
-            po.lib().orc_mh_step(h, C.byref(r.s), C.byref(t), Q, C.byref(cur), 1, None)
-        po.lib().orc_proposer_free(h)
-        np.testing.assert_allclose(P[w], Q, rtol=1e-11)
-        assert lk[w] == pytest.approx(cur.value, rel=1e-9)
+    for w in ((0, 127, 128, 255) if tt else (0, 63, 64, 129) if tight else (0, 5, 64, 95)):
+        ij, kl = walker_seed(*seeds, w)
+        acc, Ps, curs, trials = _cal_oracle_chain(orc, th[w], pmin, pmax, pm, ps, T, ij, kl, steps, P0)
+        if tight:
+            _assert_visits_edges(acc, trials, f"{case} walker {w}")
+        np.testing.assert_allclose(P[w], Ps[-1], rtol=1e-11)
+        assert lk[w] == pytest.approx(curs[-1], rel=1e-9)
 
 
 def test_history_stats():
@@ -288,7 +369,8 @@ def test_convergence_exchange_on_device():
     assert np.all(np.isfinite(s.state()[1]))
 
 
-@pytest.mark.parametrize("name", ["gauss6_drag", "gauss4_drag_every_step", "gauss27_fast21_drag"])
+@pytest.mark.parametrize("name", ["gauss6_drag", "gauss4_drag_every_step", "gauss27_fast21_drag",
+                                  "gauss6_drag_tight_T2"])
 def test_walker0_follows_reference_dragging(rng_golden, name):
     """cmbs_step_drag: walker 0 (seeded as the reference chain) follows the
     reference TFastDraggingSampler chain step by step; every walker follows
@@ -363,6 +445,143 @@ def test_dragging_with_plik_theory_callback(tmp_path):
         assert terms[w] == pytest.approx(orc.loglike(th[w], P[w, 1]), rel=1e-9)
 
 
+def _scaled_plik_target(orc, bh, pmin, pmax, pm, ps, T, extra_like=None):
+    """orc_target_t of plik_lite on theory = P(1) x base (plik_scale_index 1)
+    with calPlanck = P(2), priors and Temperature T; returns (target, keep)."""
+    keep = [np.ascontiguousarray(a, dtype=np.float64) for a in (pmin, pmax, pm, ps)]
+    t = po.Target()
+    t.num_params = 2
+    t.pmin, t.pmax, t.prior_mean, t.prior_std = [a.ctypes.data for a in keep]
+    t.temperature = T
+    t.plik, t.plik_nuis_index, t.plik_dl, t.plik_ld_field = orc.h, 2, bh.ctypes.data, bh.shape[1]
+    t.plik_scale_index = 1
+    if extra_like is not None:
+        keep.append(po.EXTRA_LIKE_FN(extra_like))
+        t.extra_like = C.cast(keep[-1], C.c_void_p)
+    return t, keep
+
+
+DRAG_W, DRAG_STEPS, DRAG_T, DRAG_SEEDS, DRAG_WALKERS = 130, 24, 2.0, (95, 96), (0, 63, 64, 129)
+DRAG_PMIN, DRAG_PMAX = np.array([TIGHT_A[0], TIGHT_CAL[0]]), np.array([TIGHT_A[1], TIGHT_CAL[1]])
+DRAG_PM, DRAG_PS = np.array([0.0, 1.0]), np.array([0.0, 0.0025])
+DRAG_COV = np.diag([0.003 ** 2, 0.0025 ** 2])
+
+
+def _drag_oracle_chains(data, bh):
+    """orc_drag_step chains (oversample_fast 2: fast steps and drags alternate)
+    of test_dragging_plik_follows_oracle_at_bounds' checked walkers.  An
+    extra_like probe that returns 0.0 counts the in-bounds evaluations of every
+    step: a full drag makes 7.  Per walker: (accept, P, CurLike, calls, is_drag)
+    per step and the final mult; asserts that the walkers together visit the
+    edges."""
+    from cosmomc_amd.sampler import walker_seed
+    orc = po.PlikLite(data)
+    chains = {}
+    for w in DRAG_WALKERS:
+        calls = [0]
+
+        def probe(user, Pp, calls=calls):
+            calls[0] += 1
+            return 0.0
+        t, keep = _scaled_plik_target(orc, bh, DRAG_PMIN, DRAG_PMAX, DRAG_PM, DRAG_PS, DRAG_T, extra_like=probe)
+        h = po.lib().orc_proposer_create(2, np.array([1, 1], dtype=np.int32), np.array([1, 2], dtype=np.int32),
+                                         1, 2, 2.4, 2, np.array([1, 2], dtype=np.int32))
+        po.lib().orc_proposer_set_covariance(h, np.ascontiguousarray(DRAG_COV))
+        r = po.Ranmar(*walker_seed(*DRAG_SEEDS, w))
+        Q = np.array([1.0, 1.0])
+        cur = C.c_double(po.lib().orc_target_loglike(C.byref(t), Q))
+        st = po.DragState(0, 0.0, 3.0, 2)                   # SampleFrom starts with mult = 0 (MCMC.f90:141)
+        acc, Ps, curs, ncall, drag = [], [], [], [], []
+        for _ in range(DRAG_STEPS):
+            calls[0] = 0
+            acc.append(bool(po.lib().orc_drag_step(h, C.byref(r.s), C.byref(t), C.byref(st), Q, C.byref(cur))))
+            Ps.append(Q.copy())
+            curs.append(cur.value)
+            ncall.append(calls[0])
+            drag.append(st.num_drag % 2 == 0)
+        po.lib().orc_proposer_free(h)
+        chains[w] = (np.array(acc), np.array(Ps), np.array(curs), np.array(ncall), np.array(drag), st.mult)
+        print(f"drag walker {w}: {int(np.sum(acc))} accepts; calls of its drags {np.array(ncall)[np.array(drag)]}, "
+              f"accepted {np.array(acc)[np.array(drag)].astype(int)}")
+        assert np.sum(acc) >= 2, (w, acc)
+    drags = [(n, a) for c in chains.values() for n, a, d in zip(c[3], c[0], c[4]) if d]
+    assert any(n == 0 for n, _ in drags), "no drag was aborted at its end point"
+    assert any(n in (3, 5) for n, _ in drags), "no drag went out of bounds inside the interpolation loop"
+    assert any(n == 7 and a for n, a in drags), "no full drag was accepted"
+    return chains
+
+
+def test_dragging_plik_follows_oracle_at_bounds(tmp_path):
+    """Dragging with a data likelihood, step by step, at the bounds and at
+    Temperature 2: plik_lite on theory = A x base from the theory callback
+    (as test_dragging_with_plik_theory_callback), W = 130, 24 step_drag(1)
+    calls with oversample_fast 2, A in [0.998, 1.003], calPlanck in
+    [0.997, 1.004].  drag_staged_kernel (the default) and drag_kernel
+    (cmamd_debug_drag_hbm) give the same bits, and walkers 0, 63, 64 and 129
+    follow orc_drag_step: every accept decision, P (rtol 1e-11) and CurLike
+    (rel 1e-9) after every step, mult at the end.  After every step the
+    walker's theory row is P[w, 0] x base (rtol 1e-15), and a rejected step
+    leaves it unchanged bit for bit (drag_swap_theory must not copy a rejected
+    end point's theory).
+
+    The oracle's 12 drags per walker (counted by an extra_like probe, 7
+    in-bounds evaluations in a full drag; seeds (95, 96)) make
+    [0 7 0 0 0 5 5 0 0 0 0 1], [1 0 3 0 0 3 0 0 0 5 0 7],
+    [0 3 7 0 0 0 0 7 0 0 1 0] and [0 3 0 3 0 0 0 0 3 0 5 0] evaluations: 31
+    drags aborted at the end point, 10 that left the bounds inside the
+    interpolation loop, 4 full drags of which 2 were accepted; the walkers
+    accept 3, 5, 4 and 7 of their 24 steps.  The test asserts at least one
+    aborted drag (0), one with 3 or 5, one accepted full drag and at least 2
+    accepts per walker."""
+    from cosmomc_amd import _native as N
+    from cosmomc_amd.likelihood import NativeCMBLikelihood
+    from cosmomc_amd.sampler import BatchedMCMC
+    data = syn.make_plik_lite(12345)
+    bh = np.ascontiguousarray(syn.base_theory(2508)[:3])
+    chains = _drag_oracle_chains(data, bh)
+    W = DRAG_W
+    base = torch.tensor(bh, device="cuda")
+    wl = list(DRAG_WALKERS)
+    runs = []
+    for hbm in (0, 1):
+        like = NativeCMBLikelihood("PLIK_LITE", data.write(str(tmp_path / f"h{hbm}")))
+        like.nuisance_indices = [2]
+        theory = base.unsqueeze(0).repeat(W, 1, 1).contiguous()
+        end = torch.empty_like(theory)
+        s = BatchedMCMC(W, 2, [1, 2], [[1], [2]], 1, DRAG_PMIN, DRAG_PMAX, DRAG_PM, DRAG_PS, oversample_fast=2,
+                        propose_scale=2.4, temperature=DRAG_T, seed_ij=DRAG_SEEDS[0], seed_kl=DRAG_SEEDS[1])
+        s.set_covariance(DRAG_COV)
+        s.add_likelihood(like, theory)
+        assert N.lib().cmamd_debug_drag_hbm(s._h, hbm) == 0
+        s.set_drag_theory(0, end)
+        s.set_start(np.tile([1.0, 1.0], (W, 1)))
+
+        def theory_fn(P_end):
+            end.copy_(base.unsqueeze(0) * P_end[0].reshape(-1, 1, 1))
+        steps = []
+        for _ in range(DRAG_STEPS):
+            s.step_drag(1, theory_fn=theory_fn)
+            steps.append((*s.state(), theory[wl].cpu().numpy()))
+        runs.append(steps)
+        s.close()
+    for k, (a, b) in enumerate(zip(*runs)):
+        for x, y in zip(a, b):
+            assert np.array_equal(x, y), f"drag_staged_kernel and drag_kernel differ at step {k}"
+    for i, w in enumerate(DRAG_WALKERS):
+        acc, Ps, curs, _, _, mult = chains[w]
+        prevP, prevth = np.array([1.0, 1.0]), bh
+        for k, (P, lk, m, nacc, thw) in enumerate(runs[0]):
+            moved = not np.array_equal(P[w], prevP)
+            assert moved == bool(acc[k]), f"accept decision of walker {w} at step {k}"
+            np.testing.assert_allclose(P[w], Ps[k], rtol=1e-11, atol=0, err_msg=f"walker {w} step {k}")
+            assert lk[w] == pytest.approx(curs[k], rel=1e-9), (w, k)
+            np.testing.assert_allclose(thw[i], P[w, 0] * bh, rtol=1e-15, atol=0, err_msg=f"walker {w} step {k}")
+            if not moved:
+                assert np.array_equal(thw[i], prevth), f"rejected step {k} changed walker {w}'s theory"
+            prevP, prevth = P[w].copy(), thw[i]
+        assert runs[0][-1][2][w] == mult
+
+
 def test_history_terms_and_chi2_chain_files(tmp_path):
     """Per-likelihood terms of the recorded points (cmbs_history_terms_host)
     equal the oracle's plik_lite -lnL at every recorded point, and the chain
@@ -432,12 +651,25 @@ def test_deferred_combine_bitwise(tmp_path):
         assert np.array_equal(terms[k, 0], ref), np.abs(terms[k, 0] - ref).max()
 
 
-@pytest.mark.parametrize("oversample", [1, 3])
-def test_full_steps_with_theory_callback(tmp_path, oversample):
+@pytest.mark.parametrize("oversample,tight", [pytest.param(1, False, id="1"), pytest.param(3, False, id="3"),
+                                              pytest.param(1, True, id="1-tight_T2p5"),
+                                              pytest.param(3, True, id="3-tight_T2p5")])
+def test_full_steps_with_theory_callback(tmp_path, oversample, tight):
     """cmbs_step_theory: full GetNewSample steps (slow amplitude A and fast
     calPlanck) with the theory A x base recomputed at every trial point by a
     theory function.  Walkers follow the C oracle's chains (its slow-theory
-    model scales the cached theory by P(A)) and accepted walkers carry A x base."""
+    model scales the cached theory by P(A)) and accepted walkers carry A x base.
+
+    tight_T2p5: A in [0.998, 1.003], calPlanck in [0.997, 1.004], Temperature
+    2.5, one step per call.  The checked walkers follow orc_mh_step after
+    every step (accept decisions, P at rtol 1e-11, CurLike at rel 1e-9); after
+    every step the walker's theory row is P[w, 0] x base (rtol 1e-15) and a
+    rejected step leaves it unchanged bit for bit (a swap of an out-of-bounds
+    trial's theory fails here).  Over the 40 steps the oracle chains of walkers
+    0, 1, 41 and 79 have 21, 20, 23 and 23 (oversample_fast 1) / 22, 25, 23
+    and 24 (3) trials out of bounds and 9, 15, 10 and 9 / 15, 8, 11 and 6
+    accepts, of which 6, 7, 4 and 6 / 4, 2, 3 and 2 moved the slow A; the test
+    asserts at least a quarter out of bounds and 3 accepts each."""
     from cosmomc_amd.likelihood import NativeCMBLikelihood
     from cosmomc_amd.sampler import BatchedMCMC, walker_seed
     from cosmomc_amd._native import NativeError
@@ -445,14 +677,15 @@ def test_full_steps_with_theory_callback(tmp_path, oversample):
     like = NativeCMBLikelihood("PLIK_LITE", data.write(str(tmp_path)))
     like.nuisance_indices = [2]
     W, steps = 80, 40
+    T = 2.5 if tight else 1.0
     base = torch.tensor(syn.base_theory(2508)[:3], device="cuda")
     theory = base.unsqueeze(0).repeat(W, 1, 1).contiguous()
     trial = torch.empty_like(theory)
-    pmin, pmax = np.array([0.9, 0.9]), np.array([1.1, 1.1])
+    pmin, pmax = (DRAG_PMIN, DRAG_PMAX) if tight else (np.array([0.9, 0.9]), np.array([1.1, 1.1]))
     pm, ps = np.array([0.0, 1.0]), np.array([0.0, 0.0025])
     cov = np.diag([0.002 ** 2, 0.0025 ** 2])
     s = BatchedMCMC(W, 2, [1, 2], [[1], [2]], 1, pmin, pmax, pm, ps, oversample_fast=oversample,
-                    propose_scale=2.4, seed_ij=71, seed_kl=72)
+                    propose_scale=2.4, temperature=T, seed_ij=71, seed_kl=72)
     s.set_covariance(cov)
     s.add_likelihood(like, theory)
     s.set_trial_theory(0, trial)
@@ -462,34 +695,44 @@ def test_full_steps_with_theory_callback(tmp_path, oversample):
 
     def theory_fn(P_trial):
         trial.copy_(base.unsqueeze(0) * P_trial[0].reshape(-1, 1, 1))
-    s.step_theory(steps, theory_fn=theory_fn)
+    checked = (0, 1, 41, 79)
+    per_step = []
+    if tight:
+        for _ in range(steps):
+            s.step_theory(1, theory_fn=theory_fn)
+            per_step.append((*s.state()[:2], theory[list(checked)].cpu().numpy()))
+    else:
+        s.step_theory(steps, theory_fn=theory_fn)
     P, lk, mult, nacc = s.state()
     assert np.any(np.abs(P[:, 0] - 1.0) > 1e-6), "no slow move was accepted"
     th, b = theory.cpu().numpy(), base.cpu().numpy()
     orc = po.PlikLite(data)
     bh = np.ascontiguousarray(syn.base_theory(2508)[:3])
-    for w in (0, 1, 41, 79):
+    for i, w in enumerate(checked):
         np.testing.assert_allclose(th[w], P[w, 0] * b, rtol=1e-15, atol=0)
         ij, kl = walker_seed(71, 72, w)
         h = po.lib().orc_proposer_create(2, np.array([1, 1], dtype=np.int32), np.array([1, 2], dtype=np.int32),
                                          1, oversample, 2.4, 2, np.array([1, 2], dtype=np.int32))
         po.lib().orc_proposer_set_covariance(h, np.ascontiguousarray(cov))
-        t = po.Target()
-        keep = [np.ascontiguousarray(a) for a in (pmin, pmax, pm, ps)]
-        t.num_params = 2
-        t.pmin, t.pmax, t.prior_mean, t.prior_std = [a.ctypes.data for a in keep]
-        t.temperature = 1.0
-        t.plik, t.plik_nuis_index, t.plik_dl, t.plik_ld_field = orc.h, 2, bh.ctypes.data, bh.shape[1]
-        t.plik_scale_index = 1
-        r = po.Ranmar(ij, kl)
-        Q = np.array([1.0, 1.0])
-        cur = C.c_double(po.lib().orc_target_loglike(C.byref(t), Q))
-        acc = 0
-        for _ in range(steps):
-            acc += po.lib().orc_mh_step(h, C.byref(r.s), C.byref(t), Q, C.byref(cur), 0, None)
+        t, keep = _scaled_plik_target(orc, bh, pmin, pmax, pm, ps, T)
+        acc, Ps, curs, trials = _oracle_steps(h, t, po.Ranmar(ij, kl), [1.0, 1.0], steps, 0)
         po.lib().orc_proposer_free(h)
-        np.testing.assert_allclose(P[w], Q, rtol=1e-11)
-        assert lk[w] == pytest.approx(cur.value, rel=1e-9)
+        np.testing.assert_allclose(P[w], Ps[-1], rtol=1e-11)
+        assert lk[w] == pytest.approx(curs[-1], rel=1e-9)
+        if tight:
+            n_oob, n_acc, _, _ = _edge_counts(acc, trials)
+            print(f"full steps walker {w}: {n_oob} of {steps} trials out of bounds, {n_acc} accepts")
+            assert n_oob >= steps // 4 and n_acc >= 3, (w, n_oob, n_acc)
+            prevP, prevth = np.array([1.0, 1.0]), bh
+            for k, (Pk, lkk, thk) in enumerate(per_step):
+                moved = not np.array_equal(Pk[w], prevP)
+                assert moved == bool(acc[k]), f"accept decision of walker {w} at step {k}"
+                np.testing.assert_allclose(Pk[w], Ps[k], rtol=1e-11, atol=0, err_msg=f"walker {w} step {k}")
+                assert lkk[w] == pytest.approx(curs[k], rel=1e-9), (w, k)
+                np.testing.assert_allclose(thk[i], Pk[w, 0] * bh, rtol=1e-15, atol=0, err_msg=f"walker {w} step {k}")
+                if not moved:
+                    assert np.array_equal(thk[i], prevth), f"rejected step {k} changed walker {w}'s theory"
+                prevP, prevth = Pk[w].copy(), thk[i]
 
 
 def test_chain_files_from_history(tmp_path):
@@ -558,8 +801,14 @@ def test_interleaved_nuisance_indices(tmp_path):
         assert lk[w] == pytest.approx(t1 + t2 + pri, rel=1e-9)
 
 
-@pytest.mark.parametrize("shared_theory", [True, False])
-def test_change_mask_matches_dense(cmbl_golden, refdata, tmp_path, shared_theory):
+MASK_TIGHT = 0.05          # tight case: the bounds' half-widths times this (1 - 2.5 proposal sigmas)
+
+
+@pytest.mark.parametrize("shared_theory,tight", [pytest.param(True, False, id="True"),
+                                                 pytest.param(False, False, id="False"),
+                                                 pytest.param(True, True, id="True-tight_T2"),
+                                                 pytest.param(False, True, id="False-tight_T2")])
+def test_change_mask_matches_dense(cmbl_golden, refdata, tmp_path, shared_theory, tight):
     """Per-likelihood change mask (LogLikeWithTheorySet, calclike.f90:374-386):
     plik_lite (calPlanck) + BICEP/Keck/Planck (6 varying foreground parameters)
     in separate fast blocks, so every step each walker re-evaluates only the
@@ -567,7 +816,13 @@ def test_change_mask_matches_dense(cmbl_golden, refdata, tmp_path, shared_theory
     (plik and the HL CMBlikes kernels on compacted slots, theory rows gathered
     when they are per walker).  Walker groups (cmbs_set_groups) take the dense
     path, which evaluates every likelihood for every walker: both runs must
-    make the same accept decisions and end at the same points and terms."""
+    make the same accept decisions and end at the same points and terms.
+
+    tight_T2: the bounds' half-widths scaled by MASK_TIGHT (calPlanck within
+    2.5 proposal sigmas, the foreground parameters within 1 - 1.25) and
+    Temperature 2, so many trials of either block are logZero in the sparse
+    path's bounds verdict: at least a quarter of the walkers sit on mult > 1
+    after the 24 steps (asserted), and the rest as in the wide case."""
     import os
     from cosmomc_amd.likelihood import NativeCMBLikelihood
     from cosmomc_amd.sampler import BatchedMCMC
@@ -587,13 +842,16 @@ def test_change_mask_matches_dense(cmbl_golden, refdata, tmp_path, shared_theory
     vary = [2, 3, 4, 5, 6, 8, 9]                      # calPlanck, Adust, Async, alphadust, betadust, alphasync, betasync
     pmin, pmax = P0.copy(), P0.copy()
     for i, wdt in zip(vary, [0.1, 2.0, 1.0, 0.5, 0.5, 1.0, 1.0]):
+        wdt *= MASK_TIGHT if tight else 1.0
         pmin[i - 1], pmax[i - 1] = P0[i - 1] - wdt, P0[i - 1] + wdt
+    T = 2.0 if tight else 1.0
     pm, ps = np.zeros(18), np.zeros(18)
     pm[1], ps[1] = 1.0, 0.0025
     sig = np.array([0.002, 0.1, 0.05, 0.02, 0.02, 0.05, 0.05])
     runs = []
     for g in (1, 2):
-        s = BatchedMCMC(W, 18, vary, [[1], [2, 3, 4, 5, 6, 7]], 0, pmin, pmax, pm, ps, seed_ij=41, seed_kl=42)
+        s = BatchedMCMC(W, 18, vary, [[1], [2, 3, 4, 5, 6, 7]], 0, pmin, pmax, pm, ps, temperature=T,
+                        seed_ij=41, seed_kl=42)
         s.set_covariance(np.diag(sig ** 2))
         s.set_groups(g)
         s.add_likelihood(plik, dl)
@@ -606,6 +864,10 @@ def test_change_mask_matches_dense(cmbl_golden, refdata, tmp_path, shared_theory
         s.close()
     a, b = runs
     assert np.all(a[3] > 0)
+    if tight:
+        print(f"change mask, tight bounds: {np.mean(a[2] > 1):.2f} of the walkers on mult > 1, "
+              f"fewest accepts {a[3].min()}")
+        assert np.mean(a[2] > 1) >= 0.25
     np.testing.assert_array_equal(a[3], b[3])
     np.testing.assert_array_equal(a[2], b[2])
     np.testing.assert_array_equal(a[0], b[0])
@@ -919,6 +1181,70 @@ def test_dragging_fused_plik_lensing(cmbl_golden, refdata, tmp_path):
         assert lk[w] == pytest.approx(ref, rel=1e-12)
 
 
+def test_dragging_fused_plik_lensing_at_bounds(cmbl_golden, refdata, tmp_path):
+    """test_dragging_fused_plik_lensing with A in [0.998, 1.003], calPlanck in
+    [0.997, 1.004] and Temperature 2 (slow steps of 0.0048 and fast steps of
+    0.006: most end points and many interpolation points are out of bounds):
+    the interpolation steps paired into two launches (cmamd_debug_drag_pair 1,
+    the default) and run one after the other (0) give the same bits, every
+    checked walker's final theory row is A_w x base, its terms are the oracles'
+    there and CurLike = (plik + lensing) / T + prior / T."""
+    import os
+
+    import cmblikes_oracle as co
+    from cosmomc_amd import _native as N
+    from cosmomc_amd.likelihood import NativeCMBLikelihood
+    from cosmomc_amd.sampler import BatchedMCMC
+    c = cmbl_golden["cases"]["lensing_consext8"]
+    data = syn.make_plik_lite(12345)
+    W, T = 130, 2.0
+    base = torch.tensor(syn.walker_theory(1, seed=4, n_fields=10, ld_field=2512), device="cuda")[0]
+    pmin, pmax = np.array([TIGHT_A[0], TIGHT_CAL[0]]), np.array([TIGHT_A[1], TIGHT_CAL[1]])
+    pm, ps = np.array([0.0, 1.0]), np.array([0.0, 0.0025])
+    out = []
+    for pair in (1, 0):
+        plik = NativeCMBLikelihood("PLIK_LITE", data.write(str(tmp_path / f"p{pair}")))
+        lens = NativeCMBLikelihood(c["tag"], os.path.join(refdata, c["dataset"]), c["overrides"])
+        plik.nuisance_indices = [2]
+        lens.nuisance_indices = [2]
+        theory = base.unsqueeze(0).repeat(W, 1, 1).contiguous()
+        end = torch.empty_like(theory)
+        s = BatchedMCMC(W, 2, [1, 2], [[1], [2]], 1, pmin, pmax, pm, ps, propose_scale=2.4, temperature=T,
+                        seed_ij=93, seed_kl=94)
+        s.set_covariance(np.diag([0.002 ** 2, 0.0025 ** 2]))
+        s.add_likelihood(plik, theory)
+        s.add_likelihood(lens, theory)
+        assert N.lib().cmamd_debug_fused(s._h) > 0
+        assert N.lib().cmamd_debug_drag_pair(s._h, pair) == 0
+        s.set_drag_theory(0, end)
+        s.set_drag_theory(1, end)
+        s.set_start(np.tile([1.0, 1.0], (W, 1)))
+        s.enable_history(64)
+
+        def theory_fn(P_end):
+            torch.mul(base.unsqueeze(0), P_end[0].reshape(-1, 1, 1), out=end)
+        s.step_drag(12, theory_fn=theory_fn)
+        n = s.history_count()
+        out.append((s.history_host(0, n), s.history_terms(0, n), *s.state(), theory.cpu().numpy()))
+        s.close()
+    for x, y in zip(*out):
+        assert np.array_equal(x, y)
+    hist, terms, P, lk, mult, nacc, th = out[0]
+    terms = terms[-1]
+    assert np.any(np.abs(P[:, 0] - 1.0) > 1e-6), "no drag was accepted"
+    assert np.all((P >= pmin) & (P <= pmax))
+    assert np.mean(mult > 1) >= 0.25                      # a good share of the last steps were rejected
+    b = base.cpu().numpy()
+    op = po.PlikLite(data)
+    ol = co.CMBLikesOracle(os.path.join(refdata, c["dataset"]), c["overrides"], c["tag"])
+    for w in (0, 64, W - 1):
+        np.testing.assert_allclose(th[w], P[w, 0] * b, rtol=1e-15, atol=0)
+        assert terms[0, w] == pytest.approx(op.loglike(th[w, :3], P[w, 1]), rel=1e-9)
+        assert terms[1, w] == pytest.approx(ol.loglike(th[w], P[w, 1:2]), rel=1e-10)
+        ref = (terms[0, w] + terms[1, w]) / T + 0.5 * ((P[w, 1] - 1.0) / 0.0025) ** 2 / T
+        assert lk[w] == pytest.approx(ref, rel=1e-12)
+
+
 @pytest.mark.parametrize("W", [130, 1024])
 def test_drag_staged_matches_hbm(cmbl_golden, refdata, tmp_path, W):
     """The drag stages on an LDS image of the walkers' state (drag_staged_kernel,
@@ -1057,20 +1383,12 @@ def test_rotation_rows_in_place_match_staged(blocks, W, force):
     assert a == b
 
 
-@pytest.mark.parametrize("W,shared", [(512, True), (200, False)])
-def test_bin_corun_bitwise(tmp_path, W, shared):
-    """The bin co-run (config4_fast21's schedule: plik_lite binned into raw
-    sums inside the proposing launch, its quadratic form forming Delta = X -
-    S / cal^2 from them) leaves every walker's state, history row and
-    likelihood terms bit-identical to the unpipelined steps (plik_bin_delta +
-    quadform_ksplit), across the 21-wide block's rotations (rot_kernel between
-    the proposing launch and the quadratic form); the walkers' terms match
-    the plik_lite oracle."""
-    from cosmomc_amd import _native as N
-    from cosmomc_amd.likelihood import NativeCMBLikelihood
-    from cosmomc_amd.sampler import BatchedMCMC
+def _bin_corun_problem(W, shared, tight):
+    """test_bin_corun_bitwise's problem: calPlanck + 20 test-Gaussian
+    parameters in one 21-wide fast block.  tight: every bound at BIN_TIGHT
+    proposal widths from the centre (in place of 20; calPlanck in place of
+    [0.9, 1.1]) and starts spread over a quarter of that."""
     n = 21
-    data = syn.make_plik_lite(12345)
     rng = np.random.default_rng(2121)
     width = np.concatenate([[0.0025], rng.uniform(0.05, 2.0, n - 1)])
     A = rng.standard_normal((n - 1, n - 1))
@@ -1080,22 +1398,82 @@ def test_bin_corun_bitwise(tmp_path, W, shared):
     cov[0, 0] = 1.0
     cov[1:, 1:] = corr / d[:, None] / d[None, :] * np.outer(width[1:], width[1:])
     P0 = np.concatenate([[1.0], rng.uniform(-1.0, 1.0, n - 1)])
-    pmin, pmax = P0 - 20 * width, P0 + 20 * width
-    pmin[0], pmax[0] = 0.9, 1.1
+    f = BIN_TIGHT if tight else 20
+    pmin, pmax = P0 - f * width, P0 + f * width
+    if not tight:
+        pmin[0], pmax[0] = 0.9, 1.1
     pm, ps = np.zeros(n), np.zeros(n)
     pm[0], ps[0] = 1.0, 0.0025
-    used = list(range(1, n + 1))
     th = syn.walker_theory(1 if shared else W, seed=5, n_fields=3, ld_field=2512)
+    g = syn.gaussians(123, W * n).reshape(W, n)
+    start = np.clip(P0 + (0.25 * f if tight else 2) * width * g, pmin + 1e-9, pmax - 1e-9)
+    return n, width, cov, P0, pmin, pmax, pm, ps, th, start
+
+
+BIN_TIGHT = 2.0
+
+
+def _bin_corun_oracle_chain(data, prob, w, T, seeds, steps):
+    """One walker's FastParameterSample chain of the bin co-run problem on the
+    C oracle: the test Gaussian and plik_lite together (orc_target_loglike)."""
+    from cosmomc_amd.sampler import walker_seed
+    n, width, cov, P0, pmin, pmax, pm, ps, th, start = prob
+    used = np.arange(1, n + 1, dtype=np.int32)
+    h = po.lib().orc_proposer_create(1, np.array([n], dtype=np.int32), used, 0, 1, 2.4, n, used)
+    po.lib().orc_proposer_set_covariance(h, np.ascontiguousarray(np.diag(width ** 2)))
+    covinv = np.array(cov, dtype=np.float64, order="C")          # a copy: orc_matrix_inverse works in place
+    assert po.lib().orc_matrix_inverse(covinv, n) == 0
+    keep = [np.ascontiguousarray(a, dtype=np.float64) for a in (pmin, pmax, pm, ps, P0)]
+    dlw = np.ascontiguousarray(th[w if th.shape[0] > 1 else 0])
+    orc = po.PlikLite(data)
+    t = po.Target()
+    t.num_params = n
+    t.pmin, t.pmax, t.prior_mean, t.prior_std, t.center = [a.ctypes.data for a in keep]
+    t.temperature = T
+    t.test_like, t.n_used, t.params_used, t.test_covinv = 1, n, used.ctypes.data, covinv.ctypes.data
+    t.plik, t.plik_nuis_index, t.plik_dl, t.plik_ld_field = orc.h, 1, dlw.ctypes.data, dlw.shape[1]
+    out = _oracle_steps(h, t, po.Ranmar(*walker_seed(*seeds, w)), start[w], steps, 1)
+    po.lib().orc_proposer_free(h)
+    return out
+
+
+@pytest.mark.parametrize("W,shared,tight", [pytest.param(512, True, False, id="512-True"),
+                                            pytest.param(200, False, False, id="200-False"),
+                                            pytest.param(200, False, True, id="200-False-tight_T2")])
+def test_bin_corun_bitwise(tmp_path, W, shared, tight):
+    """The bin co-run (config4_fast21's schedule: plik_lite binned into raw
+    sums inside the proposing launch, its quadratic form forming Delta = X -
+    S / cal^2 from them) leaves every walker's state, history row and
+    likelihood terms bit-identical to the unpipelined steps (plik_bin_delta +
+    quadform_ksplit), across the 21-wide block's rotations (rot_kernel between
+    the proposing launch and the quadratic form); the walkers' terms match
+    the plik_lite oracle.
+
+    tight_T2: every bound at 2 proposal widths from the centre and
+    Temperature 2.  Besides the bitwise comparison, walkers 0, 63, 64 and 199
+    follow the C oracle's chain (test Gaussian + plik_lite) over the 44 steps:
+    every accept decision, and P and CurLike at the wide reference chains'
+    tolerances (rtol 1e-10 / atol 1e-11: 21-wide rotations; rel 1e-9).  Those
+    oracle chains have 19, 20, 31 and 22 of their 44 trials out of bounds, 18,
+    11, 9 and 16 accepts, 7, 13, 4 and 6 in-bounds rejections and 6, 5, 6 and 6
+    accepts right after an out-of-bounds trial (_assert_visits_edges)."""
+    from cosmomc_amd import _native as N
+    from cosmomc_amd.likelihood import NativeCMBLikelihood
+    from cosmomc_amd.sampler import BatchedMCMC
+    data = syn.make_plik_lite(12345)
+    prob = _bin_corun_problem(W, shared, tight)
+    n, width, cov, P0, pmin, pmax, pm, ps, th, start = prob
+    T = 2.0 if tight else 1.0
+    used = list(range(1, n + 1))
     dl = torch.tensor(th, device="cuda")
     if shared:
         dl = dl.expand(W, th.shape[1], th.shape[2])
-    g = syn.gaussians(123, W * n).reshape(W, n)
-    start = np.clip(P0 + 2 * width * g, pmin + 1e-9, pmax - 1e-9)
     out = []
     for mode in (3, 0):
         plik = NativeCMBLikelihood("PLIK_LITE", data.write(str(tmp_path / f"m{mode}")))
         plik.nuisance_indices = [1]
-        smp = BatchedMCMC(W, n, used, [used], 0, pmin, pmax, pm, ps, propose_scale=2.4, seed_ij=4004, seed_kl=9373)
+        smp = BatchedMCMC(W, n, used, [used], 0, pmin, pmax, pm, ps, propose_scale=2.4, temperature=T, seed_ij=4004,
+                          seed_kl=9373)
         smp.set_covariance(np.diag(width ** 2))
         smp.set_test_gaussian(cov, P0)
         smp.add_likelihood(plik, dl)
@@ -1120,6 +1498,11 @@ def test_bin_corun_bitwise(tmp_path, W, shared):
     for w in (0, W // 2 - 1, W - 1):   # the last history row's plik term at the walker's point
         ref = orc.loglike(th[0 if shared else w], P[w, 0])
         assert terms[-1, 0, w] == pytest.approx(ref, rel=1e-9)
+    if tight:
+        for w in (0, 63, 64, W - 1):
+            acc, Ps, curs, trials = _bin_corun_oracle_chain(data, prob, w, T, (4004, 9373), 44)
+            _assert_visits_edges(acc, trials, f"bin co-run walker {w}")
+            _assert_follows(acc, Ps, curs, a[0], start[w], w, "bin co-run", rtol=1e-10, atol=1e-11)
 
 
 def _config5_sampler(refdata, tmp_path, W, groups, tdust_free=False):
@@ -1338,3 +1721,131 @@ def test_binned_cache_same_bits(tmp_path):
     assert np.any(a[5] > 0)
     for x, y in zip(a, b):
         np.testing.assert_array_equal(x, y)
+
+
+SCHED_W, SCHED_STEPS, SCHED_T, SCHED_SEEDS, SCHED_WALKERS = 130, 40, 2.5, (55, 66), (0, 63, 64, 129)
+SCHED_P0 = np.array([0.0222, 1.0, 3.05])
+SCHED_PMIN, SCHED_PMAX = np.array([0.0222, TIGHT_CAL[0], 3.05]), np.array([0.0222, TIGHT_CAL[1], 3.05])
+SCHED_PM, SCHED_PS = np.array([0.0, 1.0, 0.0]), np.array([0.0, 0.0025, 0.0])
+
+
+def _sched_oracle_chains(data, th, lens_oracle):
+    """The oracle chains of test_fast_schedules_bounds_and_temperature's
+    checked walkers (plik_lite + lensing + calPlanck prior over Temperature
+    2.5, calPlanck in TIGHT_CAL), each asserted to visit the edges."""
+    from cosmomc_amd.sampler import walker_seed
+    plik = po.PlikLite(data)
+    chains = {}
+    for w in SCHED_WALKERS:
+        dlw = np.ascontiguousarray(th[w])
+
+        def lensing_term(user, Pp, dlw=dlw):
+            return float(lens_oracle.loglike(dlw, np.array([Pp[1]])))
+        ij, kl = walker_seed(*SCHED_SEEDS, w)
+        chains[w] = _cal_oracle_chain(plik, dlw, SCHED_PMIN, SCHED_PMAX, SCHED_PM, SCHED_PS, SCHED_T, ij, kl,
+                                      SCHED_STEPS, SCHED_P0, extra_like=lensing_term)
+        _assert_visits_edges(chains[w][0], chains[w][3], f"schedules walker {w}")
+    return chains
+
+
+def _sched_run(c, refdata, data, tmp_path, dl, mode, lean, cache, groups, check=None):
+    """One run of the tight-bounds schedule problem: pipeline mode (-1: the
+    default), lean chain, binned cache, walker groups.  Returns (history rows,
+    history terms, P, CurLike, mult, num_accept); check(hist, terms, plik,
+    lens) runs while the likelihoods are alive."""
+    import os
+
+    from cosmomc_amd import _native as N
+    from cosmomc_amd.likelihood import NativeCMBLikelihood
+    from cosmomc_amd.sampler import BatchedMCMC
+    plik = NativeCMBLikelihood("PLIK_LITE", data.write(str(tmp_path)))
+    lens = NativeCMBLikelihood(c["tag"], os.path.join(refdata, c["dataset"]), c["overrides"])
+    plik.nuisance_indices = [2]
+    lens.nuisance_indices = [2]
+    s = BatchedMCMC(SCHED_W, 3, [2], [[1]], 0, SCHED_PMIN, SCHED_PMAX, SCHED_PM, SCHED_PS, propose_scale=2.4,
+                    temperature=SCHED_T, seed_ij=SCHED_SEEDS[0], seed_kl=SCHED_SEEDS[1])
+    s.set_covariance(np.array([[0.002 ** 2]]))
+    if groups > 1:
+        s.set_groups(groups)
+    s.add_likelihood(plik, dl)
+    s.add_likelihood(lens, dl)
+    if cache:
+        s.set_binned_cache(True)
+    if mode >= 0:
+        assert N.lib().cmamd_debug_pipeline(s._h, mode) == 0
+    if (mode, lean) != (-1, 1):
+        assert N.lib().cmamd_debug_lean(s._h, lean) == 0
+    s.enable_history(SCHED_STEPS)
+    s.set_start(np.tile(SCHED_P0, (SCHED_W, 1)))
+    for n in SCHED_CALLS:
+        s.step(n, fast_only=True)
+    out = (s.history_host(0, SCHED_STEPS), s.history_terms(0, SCHED_STEPS), *s.state())
+    assert plik.status() == 0 and lens.status() == 0             # no hand-off gave up
+    if check is not None:
+        check(out[0], out[1], plik, lens)
+    s.close()
+    return out
+
+
+SCHED_CALLS = (1, 2, 5, 32)
+
+
+def test_fast_schedules_bounds_and_temperature(cmbl_golden, refdata, tmp_path):
+    """Out-of-bounds trials and Temperature /= 1 on every fast-step schedule
+    with data likelihoods (GetLogLike, calclike.f90:97-151: a trial outside
+    [PMin, PMax] is logZero and rejected without a randexp1 draw; AddLikeTemp
+    divides the main term and the prior by Temperature; a rejected trial leaves
+    CurLike and the terms untouched).  plik_lite TTTEEE + Planck lensing on
+    per-walker theory, W = 130 (two 64-walker tiles and a tail of 2), 40 steps
+    over step() calls of 1, 2, 5 and 32, Temperature 2.5, calPlanck bounded to
+    [0.997, 1.004] round the start 1.0 with proposal steps of 0.0048.
+
+    Schedules: the default (unified launch, lean chain), (pipeline, lean) =
+    (3, 1), (0, 1), (3, 0), (0, 0), the default with the binned cache
+    (mh_tail_kernel) and the default with two walker groups (which evaluate the
+    fused pair for the whole walker set between the groups' Metropolis
+    launches).  Histories, terms and the final state are bit-identical across
+    all of them.
+
+    Walkers 0, 63, 64 and 129 follow the C oracle's chain (orc_mh_step on
+    pyoracle.PlikLite + the lensing numpy oracle + the prior, Temperature 2.5)
+    step by step: accept decisions exactly, P at rtol 1e-11, CurLike at rel
+    1e-9.  Those oracle chains have 19, 25, 18 and 27 of their 40 trials out
+    of bounds, 8, 6, 8 and 3 accepts, 13, 9, 14 and 10 in-bounds rejections
+    and 2, 3, 3 and 2 accepts right after an out-of-bounds trial (asserted).
+
+    At every recorded step the terms equal each likelihood's own loglike_batch
+    at the recorded calibration (rtol 1e-12) and CurLike = (plik + lensing) /
+    T + 0.5 z^2 / T (rel 1e-12): a rejected trial's term reaching cur_terms or
+    a temperature applied to one term only fails here."""
+    import os
+
+    import cmblikes_oracle as co
+    c = cmbl_golden["cases"]["lensing_consext8"]
+    data = syn.make_plik_lite(12345)
+    T = SCHED_T
+    assert sum(SCHED_CALLS) == SCHED_STEPS
+    th = syn.walker_theory(SCHED_W, seed=3, n_fields=10, ld_field=2512)
+    chains = _sched_oracle_chains(data, th, co.CMBLikesOracle(os.path.join(refdata, c["dataset"]), c["overrides"],
+                                                              c["tag"]))
+    dl = torch.tensor(th, device="cuda")
+
+    def no_trace(hist, terms, plik, lens):                           # rejected trials leave no trace
+        for k in range(SCHED_STEPS):
+            cal = hist[k, 0, :].copy()
+            nu = torch.tensor(cal, device="cuda").reshape(-1, 1)
+            np.testing.assert_allclose(terms[k, 0], plik.loglike_batch(dl, nu).cpu().numpy(), rtol=1e-12)
+            np.testing.assert_allclose(terms[k, 1], lens.loglike_batch(dl, nu).cpu().numpy(), rtol=1e-12)
+            z = (cal - 1.0) / 0.0025
+            np.testing.assert_allclose(hist[k, 1], (terms[k, 0] + terms[k, 1]) / T + 0.5 * z * z / T,
+                                       rtol=1e-12, atol=0, err_msg=f"CurLike at step {k}")
+    ref = _sched_run(c, refdata, data, tmp_path, dl, -1, 1, False, 1, check=no_trace)
+    for w in SCHED_WALKERS:
+        acc, Ps, curs, _ = chains[w]
+        _assert_follows(acc, Ps[:, 1:2], curs, ref[0], SCHED_P0[1:2], w, "schedules")
+    # (pipeline mode, lean chain, binned cache, walker groups)
+    for sched in ((3, 1, False, 1), (0, 1, False, 1), (3, 0, False, 1), (0, 0, False, 1), (-1, 1, True, 1),
+                  (-1, 1, False, 2)):
+        o = _sched_run(c, refdata, data, tmp_path, dl, *sched)
+        for x, y in zip(ref, o):
+            assert np.array_equal(x, y), f"schedule {sched} differs from the default"

@@ -98,8 +98,28 @@ def make_oracle_proposer(ch):
 
 
 MH_CHAINS = ["gauss6_single_block", "gauss6_blocked", "gauss6_fast_only", "gauss3_n1_blocks",
-             "gauss27_fast21_fast_only", "gauss27_fast21_os3", "gauss27_fast12_9_lincomb", "gauss40_slow_fast"]
-DRAG_CHAINS = ["gauss6_drag", "gauss4_drag_every_step", "gauss27_fast21_drag"]
+             "gauss27_fast21_fast_only", "gauss27_fast21_os3", "gauss27_fast12_9_lincomb", "gauss40_slow_fast",
+             "gauss6_fast_only_tight_T2p5", "gauss3_n1_blocks_tight_T0p5"]
+DRAG_CHAINS = ["gauss6_drag", "gauss4_drag_every_step", "gauss27_fast21_drag", "gauss6_drag_tight_T2"]
+# bounds at 1.5 sigma and Temperature /= 1 (oracle/gen_golden.py CHAIN_CASES): name -> temperature
+TIGHT_CHAINS = {"gauss6_fast_only_tight_T2p5": 2.5, "gauss3_n1_blocks_tight_T0p5": 0.5, "gauss6_drag_tight_T2": 2.0}
+
+
+@pytest.mark.parametrize("name", list(TIGHT_CHAINS))
+def test_tight_chains_have_the_shape_they_claim(rng_golden, name):
+    """The tight-bounds chains visit the edges in the reference's own run: the
+    Metropolis chains have 20-70 % of their trials at logZero (132 and 127 of
+    240), at least one accept right after a logZero trial (58 and 44), and every
+    chain at least 15 accepts (96, 76 and 75) at a temperature other than 1."""
+    ch = rng_golden["chains"][name]
+    assert ch["temperature"] == TIGHT_CHAINS[name] and ch["extra"]["bound_sigmas"] == 1.5
+    assert ch["steps"] <= 240
+    assert sum(ch["accept"]) == ch["n_accept"] >= 15
+    assert np.all(np.array(ch["P0"]) > ch["pmin"]) and np.all(np.array(ch["P0"]) < ch["pmax"])
+    if ch["fast_only"] != 2:                                  # dragging has no per-step trial value
+        assert 0.2 * ch["steps"] <= ch["n_logzero"] <= 0.7 * ch["steps"]
+        assert ch["n_accept_after_logzero"] >= 1
+        assert any(v == 1e30 for v in ch["trial_like"])       # and some are among the stored rows
 
 
 @pytest.mark.parametrize("name", MH_CHAINS)
