@@ -24,7 +24,6 @@
 //   quadform_ksplit         bigX^T C^-1 bigX / 2 on the f64 MFMA (quadform.hip).
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <cstdint>
 #include <cstring>
 #include <fstream>
@@ -42,10 +41,7 @@ static constexpr int CL_MAXREQ = 32;            // required maps
 static constexpr int BK_NPARAM = 16;            // BKPlanck.paramnames
 static constexpr int WK_COLS = 32;              // window columns per work item (two 16-row MFMA blocks)
 static constexpr int WK_CHUNK = 64;             // l per chunk
-#ifndef CMAMD_WK_NCH
-#define CMAMD_WK_NCH 4
-#endif
-static constexpr int WK_NCH = CMAMD_WK_NCH;     // chunks per work item
+static constexpr int WK_NCH = 4;     // chunks per work item
 static constexpr int WK_TS = WK_CHUNK + 2;      // LDS row stride of the spectrum tile (doubles)
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -159,10 +155,7 @@ __global__ __launch_bounds__(256) void cmbl_bk_tdtab(CLDev c, const double *__re
 // SED factors of every map (one wave per map, bandpass integrals as wave
 // reductions) and the dust / sync / dust-sync l profiles.
 //   coef[w][3][nreq] = fdust, fsync, band-centre error;  prof[w][3][L]
-#ifndef CMAMD_BKP_THREADS
-#define CMAMD_BKP_THREADS 256
-#endif
-static constexpr int BKP_THREADS = CMAMD_BKP_THREADS;   // a wave per map at a time
+static constexpr int BKP_THREADS = 256;   // a wave per map at a time
 __global__ __launch_bounds__(BKP_THREADS) void cmbl_bk_prologue(CLDev c, const double *__restrict__ nuis, long long ld_nuis,
                                                        double *__restrict__ coef, double *__restrict__ prof, int W)
 {
@@ -601,18 +594,12 @@ __global__ __launch_bounds__(256) void cmbl_window_direct(CLDev c, const double 
 // element is read once per item instead of once per pair (78 B x B pairs for
 // BK15).  l-dependent decorrelation (lform lin / quad with Delta /= 1) is
 // evaluated per value, as in the staged kernel.
-#ifndef CMAMD_GP
-#define CMAMD_GP 8
-#endif
-#ifndef CMAMD_GSEG
-#define CMAMD_GSEG 224
-#endif
 // l per grouped item: 224 (BK15's l range in three items a pair group),
 // cmbl_window_group 85.8 -> 78.1 us and configs[4] 396.4-397.8 -> 388.2-390.3
 // us/step, against 160 / 192 / 256 / 320 / 608 (406 / 417-418 / 397 / 412-414 /
-// 441 us/step; tools/gpu_r6m.sh); 6 pairs per item 400-401
-static constexpr int GP = CMAMD_GP;       // pairs per grouped item
-static constexpr int GSEG = CMAMD_GSEG;   // l per grouped item (a multiple of 32)
+// 441 us/step; DESIGN.md section 5's table); 6 pairs per item 400-401
+static constexpr int GP = 8;       // pairs per grouped item
+static constexpr int GSEG = 224;   // l per grouped item (a multiple of 32)
 static_assert(GSEG % 32 == 0, "grouped items are whole 32-l steps");
 static_assert((GP * 16 * 16 / 2) % 256 == 0, "the weight staging moves GP * 16 rows of 16 l in whole passes");
 
@@ -967,7 +954,7 @@ __device__ inline int hl_partner(int rr, int r) {   // round-robin pairing of ro
     return ((2 * rr - r) % (M - 1) + (M - 1)) % (M - 1);
 }
 
-static constexpr int HL_MAX_SWEEPS = 40;
+static constexpr int HL_MAX_SWEEPS = 40;   // as DSYEV's own iteration limit, a cap that fails loudly
 // a sweep in which no pair of a problem was further from orthogonal than
 // cos = 1e-6 is that problem's last (its own rotations leave every pair near
 // cos 1e-12: -lnL within 2.4e-14 relative of the reference's DSYEV on the BK
@@ -976,25 +963,18 @@ static constexpr int HL_MAX_SWEEPS = 40;
 // HL 173.7 / 170.9 / 167.5 us at cos 1e-6 / 1e-5 / 1e-4, golden margins
 // 2.4e-14 / 2.3e-12 / 2.1e-10, and cos 1e-4 fails the 9-map width test's
 // rtol 1e-9 (round 5, profiles/r05_hl_stop.txt)
-#ifndef CMAMD_HL_SWEEP_COS2
-#define CMAMD_HL_SWEEP_COS2 1e-12
-#endif
-static constexpr double HL_SWEEP_COS2 = CMAMD_HL_SWEEP_COS2;
-#ifndef CMAMD_HL_VFREE
-#define CMAMD_HL_VFREE 1
-#endif
-static constexpr bool HL_VFREE = CMAMD_HL_VFREE;   // as DSYEV's own iteration limit, a cap that fails loudly
+static constexpr double HL_SWEEP_COS2 = 1e-12;
 
 // One-sided (Hestenes) cyclic Jacobi of the group's symmetric M x M matrix C:
-// lane r owns column r of G (initially C's column r, i.e. its row r) and
-// column r of V (initially e_r).  A round pairs lanes (lo, hi) by the
+// lane r owns column r of G = C V (initially C's column r, i.e. its row r; V,
+// initially the identity, is not carried: see below).  A round pairs lanes (lo, hi) by the
 // round-robin circle schedule; both lanes of a pair read the other's columns
 // from LDS, form a_ll = g_l.g_l, a_hh = g_h.g_h, a_lh = g_l.g_h (the same sums
 // in the same order, so both derive the same rotation) and rotate their own
 // columns: g_l' = c g_l - s g_h, g_h' = s g_l + c g_h, with tan of the angle
 // the smaller root of t^2 + 2 zeta t - 1 = 0, zeta = (a_hh - a_ll) / (2 a_lh).
-// At convergence G = C V and V holds orthonormal eigenvectors in its columns;
-// lam = v_r . g_r = v_r^T C v_r is eigenvalue r, signed.  One column exchange
+// At convergence V holds orthonormal eigenvectors in its columns (returned in
+// V, with lam eigenvalue r, signed).  One column exchange
 // per round (two barriers) replaces the two-sided form's row exchange plus
 // broadcast of every column's rotation (three barriers, about twice the LDS
 // traffic); the column norms are carried across rounds, so a round forms one
@@ -1009,27 +989,24 @@ static constexpr bool HL_VFREE = CMAMD_HL_VFREE;   // as DSYEV's own iteration l
 // its own matrix only, not on which walkers share its wave.
 // Returns true on lanes whose pair still needed rotating in sweep
 // HL_MAX_SWEEPS (the caller fails that problem: NaN and a status bit).
-// VF (V-free): the matrices here are symmetric positive definite (C, and
+// The matrices here are symmetric positive definite (C, and
 // C^-1/2 Chat C^-1/2), so G = C V = U Sigma with U = V: eigenvalue r is the
-// norm of column r and eigenvector r that column normalised, and V need not
-// be carried -- each round exchanges and rotates one column instead of two
-// (the exchange is the round's cost: lane permutes through the LDS crossbar).
-template <int M, bool VF = false>
+// norm of column r and eigenvector r that column normalised, and V is formed
+// at the end instead of being carried -- each round exchanges and rotates one
+// column instead of two (the exchange is the round's cost: lane permutes
+// through the LDS crossbar).
+template <int M>
 __device__ bool hl_ojacobi(double (&G)[M], double (&V)[M], HLRowsLds<M> &S, int grp, int r, int lane, int which,
                            double &lam)
 {
     (void)which;
     (void)lane;
     const bool on = grp < HLRowsLds<M>::G;        // lanes past G*M idle
-    if (!VF)
+    // the input matrix (row r = column r), for the eigenvalues' signs after the solve
+    if (on)
 #pragma unroll
-        for (int k = 0; k < M; k++) V[k] = (k == r) ? 1.0 : 0.0;
-    if (VF) {   // the input matrix (row r = column r), for the eigenvalues' signs after the solve
-        if (on)
-#pragma unroll
-            for (int k = 0; k < M; k++) S.g[grp].rows[0][r][k] = G[k];
-        __syncthreads();
-    }
+        for (int k = 0; k < M; k++) S.g[grp].rows[0][r][k] = G[k];
+    __syncthreads();
     bool failed = false;
     bool done = !on;                              // this lane's problem has met the sweep stop
     const unsigned long long gmask = (M == 64 ? ~0ull : ((1ull << M) - 1)) << ((on ? grp : 0) * M);
@@ -1054,12 +1031,9 @@ __device__ bool hl_ojacobi(double (&G)[M], double (&V)[M], HLRowsLds<M> &S, int 
 #ifdef CMAMD_STAMPS
             unsigned long long t2 = 0;
 #endif
-            double Gp[M], Vp[M];
+            double Gp[M];
 #pragma unroll
-            for (int k = 0; k < M; k++) {        // every permute in flight together
-                Gp[k] = __shfl(G[k], src);
-                if (!VF) Vp[k] = __shfl(V[k], src);
-            }
+            for (int k = 0; k < M; k++) Gp[k] = __shfl(G[k], src);   // every permute in flight together
             const double np_ = __shfl(nrm, src);
             if (!done) {
                 const bool low = r < p;
@@ -1083,17 +1057,11 @@ __device__ bool hl_ojacobi(double (&G)[M], double (&V)[M], HLRowsLds<M> &S, int 
 #endif
                     if (low) {
 #pragma unroll
-                        for (int k = 0; k < M; k++) {
-                            G[k] = fma(-s, Gp[k], c * G[k]);
-                            if (!VF) V[k] = fma(-s, Vp[k], c * V[k]);
-                        }
+                        for (int k = 0; k < M; k++) G[k] = fma(-s, Gp[k], c * G[k]);
                         nrm = fma(-t, alh, all);
                     } else {
 #pragma unroll
-                        for (int k = 0; k < M; k++) {
-                            G[k] = fma(s, Gp[k], c * G[k]);
-                            if (!VF) V[k] = fma(s, Vp[k], c * V[k]);
-                        }
+                        for (int k = 0; k < M; k++) G[k] = fma(s, Gp[k], c * G[k]);
                         nrm = fma(t, alh, ahh);
                     }
                 }
@@ -1131,38 +1099,31 @@ __device__ bool hl_ojacobi(double (&G)[M], double (&V)[M], HLRowsLds<M> &S, int 
         atomicAdd(&g_hl_phase[3], nround);
     }
 #endif
-    if (VF) {
-        double n2 = 0.0;
+    double n2 = 0.0;
 #pragma unroll
-        for (int k = 0; k < M; k++) n2 = fma(G[k], G[k], n2);
-        const double sg = sqrt(n2), rsg = 1.0 / sg;
+    for (int k = 0; k < M; k++) n2 = fma(G[k], G[k], n2);
+    const double sg = sqrt(n2), rsg = 1.0 / sg;
 #pragma unroll
-        for (int k = 0; k < M; k++) V[k] = n2 > 0.0 ? div_rn(G[k], sg, rsg) : (k == r ? 1.0 : 0.0);   // G[k] / sg
-        // |g_r| is |lambda_r| and g_r / |g_r| is sign(lambda_r) u_r, so the norm alone
-        // loses the sign of an eigenvalue of a matrix that is not positive definite
-        // (a trial theory C can be): lambda_r = (A v)_i / v_i at the largest |v_i|,
-        // so a negative eigenvalue stays negative and its sqrt / log give NaN, as the
-        // reference's DSYEV eigenvalues do (CMBlikes.f90:877-894)
-        int im = 0;
-        double vm = V[0];
+    for (int k = 0; k < M; k++) V[k] = n2 > 0.0 ? div_rn(G[k], sg, rsg) : (k == r ? 1.0 : 0.0);   // G[k] / sg
+    // |g_r| is |lambda_r| and g_r / |g_r| is sign(lambda_r) u_r, so the norm alone
+    // loses the sign of an eigenvalue of a matrix that is not positive definite
+    // (a trial theory C can be): lambda_r = (A v)_i / v_i at the largest |v_i|,
+    // so a negative eigenvalue stays negative and its sqrt / log give NaN, as the
+    // reference's DSYEV eigenvalues do (CMBlikes.f90:877-894)
+    int im = 0;
+    double vm = V[0];
 #pragma unroll
-        for (int k = 1; k < M; k++)
-            if (fabs(V[k]) > fabs(vm)) {
-                im = k;
-                vm = V[k];
-            }
-        double d = 0.0;
-        if (on)
+    for (int k = 1; k < M; k++)
+        if (fabs(V[k]) > fabs(vm)) {
+            im = k;
+            vm = V[k];
+        }
+    double d = 0.0;
+    if (on)
 #pragma unroll
-            for (int k = 0; k < M; k++) d = fma(S.g[grp].rows[0][im][k], V[k], d);
-        __syncthreads();   // the callers reuse the row buffers
-        lam = (d * vm < 0.0) ? -sg : sg;
-        return failed;
-    }
-    double l = 0.0;
-#pragma unroll
-    for (int k = 0; k < M; k++) l = fma(V[k], G[k], l);
-    lam = l;
+        for (int k = 0; k < M; k++) d = fma(S.g[grp].rows[0][im][k], V[k], d);
+    __syncthreads();   // the callers reuse the row buffers
+    lam = (d * vm < 0.0) ? -sg : sg;
     return failed;
 }
 
@@ -1246,7 +1207,7 @@ __global__ __launch_bounds__(64, (M <= 12 ? 2 : 1)) void cmbl_hl_rows_kernel(HLD
     HL_STAMP(q1);
     if (h.u0) to_basis(h.u0 + (long long)b * n * n);
     HL_STAMP(q2);
-    bool unconverged = hl_ojacobi<M, HL_VFREE>(A, V, S, grp, r, lane, 0, dgr);
+    bool unconverged = hl_ojacobi<M>(A, V, S, grp, r, lane, 0, dgr);
     HL_STAMP(q3);
     if (h.u0) from_basis();
     if (on) {
@@ -1326,7 +1287,7 @@ __global__ __launch_bounds__(64, (M <= 12 ? 2 : 1)) void cmbl_hl_rows_kernel(HLD
     HL_STAMP(q5);
     if (h.v0) to_basis(h.v0 + (long long)b * n * n);
     HL_STAMP(q6);
-    unconverged = hl_ojacobi<M, HL_VFREE>(A, V, S, grp, r, lane, 1, x) || unconverged;
+    unconverged = hl_ojacobi<M>(A, V, S, grp, r, lane, 1, x) || unconverged;
     HL_STAMP(q7);
     if (h.v0) from_basis();
     __syncthreads();                               // the solve's last reads of the row buffers
@@ -2649,11 +2610,7 @@ struct CMBLikes final : Like {
                       items_even && (lmax + 1 < ld_field || (lmax % 2 == 1 && lmax + 1 <= ld_field));
         if (use_group) {
             const bool gvec = ((reinterpret_cast<uintptr_t>(dl) & 15) == 0) && ld_field % 2 == 0 && ld_walker % 2 == 0;
-            static const int map_env = [] {   // A/B: CMAMD_WG_MAP=0 forces the item-per-XCD placement
-                const char *e = std::getenv("CMAMD_WG_MAP");
-                return e ? std::atoi(e) : 1;
-            }();
-            const int txcd = (map_env && tiles % 8 == 0) ? 1 : 0;
+            const int txcd = tiles % 8 == 0 ? 1 : 0;
             const int nblk = txcd ? tiles * n_gitem : 8 * tiles * ((n_gitem + 7) / 8);
             timed_launch("cmbl_window_kernel", stream, [&](hipEvent_t e0, hipEvent_t e1) {
                 if (dev.lform_dust != 0 || dev.lform_sync != 0)

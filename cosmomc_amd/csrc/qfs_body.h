@@ -114,12 +114,11 @@ __device__ __forceinline__ double qfs_load1(const double *p)
 // the epilogue's Delta_I rows during the last K step instead of loading them
 // after it, and each lane forms its own 16 Delta_I values as it sums: the
 // accept-only launch that ends a step call, where the quadratic form is the
-// critical path, 24.1-24.4 -> 21.3-21.8 us.  In the middle launches, beside
-// the pass, it measured 0.2 us slower than qfs_body_loop (the chi^2 beside it
-// slows), and distance-2 prefetch 0.7 us slower: qfs_body_loop runs there.
-// SIGNAL (the unified step launch, sampler.hip): the partials are stored
-// agent-scope (write-through) for a consumer in the same launch.
-template <int NJ, bool SIGNAL>
+// critical path, 24.1-24.4 -> 21.3-21.8 us; the middle launches, beside the
+// pass, run it too (DESIGN.md section 5's table).
+// The partials are stored agent-scope (write-through) for the Metropolis
+// workgroups of the same launch (sampler.hip's unified step launch).
+template <int NJ>
 __device__ __forceinline__ void qfs_body_nj(double *smem, int item_ix, int tile, const QFSArgs &a)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -251,19 +250,15 @@ __device__ __forceinline__ void qfs_body_nj(double *smem, int item_ix, int tile,
     sacc += __shfl_xor(sacc, 32);
     if (lk == 0) {
         double *p = q.partial + ((size_t)tile * q.n_items + item_ix) * QF_TILE + n;
-        if (SIGNAL)
-            __hip_atomic_store(p, sacc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else
-            *p = sacc;
+        __hip_atomic_store(p, sacc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
 // The quadratic form's K loop with the compiler's own loads and waits (its
 // LDS-DMA wait is vmcnt(0) per step) and the Delta_I rows loaded after it:
-// the middle launches, and items wider than two column blocks.
+// items wider than two column blocks.
 static constexpr int QFSL_TILE_D = QF_TILE * (QF_TILE + 2);
 static_assert(QFSL_TILE_D + QF_TILE + QF_MAXKB * QF_TILE + QF_TILE <= QFS_LDS_DOUBLES, "the loop body's LDS");
-template <bool SIGNAL>
 __device__ __forceinline__ void qfs_body_loop(double *smem, int item_ix, int tile, const QFSArgs &a)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -367,24 +362,19 @@ __device__ __forceinline__ void qfs_body_loop(double *smem, int item_ix, int til
     sacc += __shfl_xor(sacc, 32);
     if (lk == 0) {
         double *p = q.partial + ((size_t)tile * q.n_items + item_ix) * QF_TILE + n;
-        if (SIGNAL)
-            __hip_atomic_store(p, sacc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else
-            *p = sacc;
+        __hip_atomic_store(p, sacc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
-// DI_AHEAD: the accept-only launch (qfs_body_nj where the item allows)
-template <bool SIGNAL, bool DI_AHEAD>
 __device__ __forceinline__ void qfs_body(double *smem, int item_ix, int tile, const QFSArgs &a)
 {
     const int nJ = a.src.items[item_ix].nJ;
-    if (DI_AHEAD && nJ == 1)
-        qfs_body_nj<1, SIGNAL>(smem, item_ix, tile, a);
-    else if (DI_AHEAD && nJ == 2)
-        qfs_body_nj<2, SIGNAL>(smem, item_ix, tile, a);
+    if (nJ == 1)
+        qfs_body_nj<1>(smem, item_ix, tile, a);
+    else if (nJ == 2)
+        qfs_body_nj<2>(smem, item_ix, tile, a);
     else
-        qfs_body_loop<SIGNAL>(smem, item_ix, tile, a);
+        qfs_body_loop(smem, item_ix, tile, a);
 }
 
 }  // namespace cmamd

@@ -1,7 +1,6 @@
 // Batched symmetric quadratic form on the f64 MFMA (see quadform.h).
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <functional>
 
 #include "quadform.h"
@@ -310,10 +309,6 @@ int QuadForm::choose_kb(int /*tiles*/) {
             best = makespan;
             best_kb = kb;
         }
-    }
-    if (const char *e = std::getenv("CMAMD_QF_KB")) {   // A/B: a fixed chunk (1 .. QF_MAXKB)
-        const int k = std::atoi(e);
-        if (k >= 1 && k <= MAXKB) best_kb = k;
     }
     kb_for_tiles[tiles] = best_kb;
     return best_kb;

@@ -247,12 +247,6 @@ struct cmbs {
     size_t uni_lds = 0;
     int tail_nosignal = 0;                   // debug (cmamd_debug_tail_nosignal)
     bool binned_cache = false;               // cmbs_set_binned_cache: bin once per fast-step call
-    int qf_ahead = 1;                        // unified launch: qfs_body_nj in the middle launches too (CMAMD_QF_AHEAD=0: the loop form)
-    int fold_late_prio = 0;                  // unified launch: CMAMD_FOLD_LATE_PRIO (A/B)
-    int qf_prio = 1;                         // unified launch: the QF waves at priority 2 (CMAMD_QF_PRIO=0 off)
-    int fold_tpf = 1;                        // unified launch: CMAMD_FOLD_TPF (A/B, 1 or 2)
-    int fold_g = 1;                          // unified launch: the small chi^2 in the Metropolis workgroups
-                                             // (CMAMD_FOLD_G=0: as rows of its own, for A/B runs)
     // a pipelined hand-off that gave up (unified launch, bin co-run): the device word, its
     // pinned copy taken at the end of each step call, checked at the next
     int *pipe_status_host = nullptr;         // pinned, mapped (pipe_status_init)
@@ -280,6 +274,7 @@ namespace cmamd {
 void sampler_set_groups(cmbs *s, int n_groups);
 // a pipelined hand-off that gave up fails here (wait: for the last step call's copy)
 void sampler_check_pipe(cmbs *s, bool wait = false);
+void rot_schedule_unknown(cmbs *s);   // the rotation schedule's loop indices are no longer known (state.hip's load)
 void sampler_chain_moments(cmbs *s, int first, int last, const double *gmean, double *out, hipStream_t stream);
 void sampler_history_host(cmbs *s, int first, int count, double *out);
 void sampler_set_trial_theory(cmbs *s, int like_index, double *dl_end, long long ld_field, long long ld_walker);

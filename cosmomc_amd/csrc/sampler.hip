@@ -16,6 +16,15 @@
 // would cost a memory round trip; instead mh_kernel stages the whole
 // per-walker state (sampler.h Rows) and the shared tables into LDS with
 // independent coalesced loads, runs the chain out of LDS and writes back.
+//
+// This file holds every kernel entry point of the chain, then the host side:
+// set-up, likelihood evaluation, the step schedules.  The device bodies are
+// headers included inside namespace cmamd, in this order: mhrng.h (RANMAR),
+// mhpropose.h (walker view, proposer, target), mhstage.h (LDS staging),
+// mhwait.h (the unified launch's arrival and wait), mhlean.h and mhbody.h (the
+// lean and the general chain), mhstep.h (the unified launch's roles), mhrot.h
+// (deferred rotations), mhdrag.h (fast dragging).  The history statistics are
+// history.hip, the state image state.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -48,89 +57,13 @@ static constexpr int NB = 64;          // walker tile of the history / collector
 // 16-walker blocks a W = 1024 step spreads over 64 CUs instead of 16: each
 // block stages a quarter of the state image (round 3: 64-walker blocks, 16
 // waves, 12.9 us).
-#ifndef CMAMD_MB
-#define CMAMD_MB 16
-#endif
-static constexpr int MB = CMAMD_MB;
+static constexpr int MB = 16;
 static constexpr int MH_THREADS = 256;
 static constexpr int NV = MH_THREADS / MB;
 static_assert(NV >= QF_GROUPS && NV % QF_GROUPS == 0, "a group per split-K group sum");
 static_assert(64 % MB == 0, "blocks tile the 64-walker rows of the split-K partials");
 
-// strided per-walker column view (LDS: stride MB; HBM: stride W)
-template <class T> struct Col {
-    T *p;
-    int s;
-    __device__ T &operator[](int i) const { return p[(size_t)i * s]; }
-};
-
-// ------------------------------------------------------------ RNG (RandUtils.f90)
-
-struct Rng {
-    Col<double> u;  // u(1:97)
-    double c;
-    int i97, j97, iset;
-    double gset;
-    int nd = 0;     // draws so far (the lean chain writes back the ring entries they overwrote)
-};
-
-__device__ __forceinline__ double ranmar(Rng &r)
-{   // RandUtils.f90:350-374
-    double uni = r.u[r.i97 - 1] - r.u[r.j97 - 1];
-    if (uni < 0.0) uni += 1.0;
-    r.u[r.i97 - 1] = uni;
-    if (--r.i97 == 0) r.i97 = 97;
-    if (--r.j97 == 0) r.j97 = 97;
-    r.nd++;
-    const double cd = 7654321.0 / 16777216.0, cm = 16777213.0 / 16777216.0;
-    r.c -= cd;
-    if (r.c < 0.0) r.c += cm;
-    uni -= r.c;
-    if (uni < 0.0) uni += 1.0;
-    return uni;
-}
-
-__device__ __forceinline__ double gaussian1(Rng &r)
-{   // RandUtils.f90:156-178
-    if (r.iset == 0) {
-        double v1, v2, rr;
-        do {
-            v1 = 2.0 * ranmar(r) - 1.0;
-            v2 = 2.0 * ranmar(r) - 1.0;
-            rr = v1 * v1 + v2 * v2;
-        } while (rr >= 1.0);
-        const double fac = sqrt(-2.0 * log(rr) / rr);
-        r.gset = v1 * fac;
-        r.iset = 1;
-        return v2 * fac;
-    }
-    r.iset = 0;
-    return r.gset;
-}
-
-__device__ __forceinline__ float randexp1(Rng &r)
-{   // RandUtils.f90:189-233, REAL(4) arithmetic (built with -ffp-contract=off)
-    const float alog2 = 0.6931471805599453f, a = 5.7133631526454228f, b = 3.4142135623730950f;
-    const float c = -1.6734053240284925f, p = 0.9802581434685472f, aa = 5.6005707569738080f;
-    const float bb = 3.3468106480569850f, hh = 0.0026106723602095f, dd = 0.0857864376269050f;
-    float u = (float)ranmar(r);
-    while (u <= 0.0f) u = (float)ranmar(r);
-    float g = c;
-    u = u + u;
-    while (u < 1.0f) {
-        g = g + alog2;
-        u = u + u;
-    }
-    u = u - 1.0f;
-    if (u <= p) return g + aa / (bb - u);
-    for (;;) {
-        u = (float)ranmar(r);
-        const float y = a / (b - u);
-        const float up = (float)ranmar(r);
-        const float bu = b - u;
-        if ((up * hh + dd) * (bu * bu) <= expf(-(y + c))) return g + y;
-    }
-}
+#include "mhrng.h"
 
 __global__ void rng_init_kernel(DevCfg c, const int *ij, const int *kl)
 {   // RMARIN, RandUtils.f90:286-348
@@ -158,880 +91,12 @@ __global__ void rng_init_kernel(DevCfg c, const int *ij, const int *kl)
     c.si[c.rows.ISET * W + w] = 0;
 }
 
-// ------------------------------------------------------------ per-walker view
-
-struct Tabs {   // shared tables (LDS copies)
-    const int *ti;   // the whole int table (likelihood nuisance_indices at DevCfg::like_nidx offsets)
-    const int *blk_n, *blk_nchanged, *blk_changed_off, *blk_map_off, *blk_R_off, *changed, *pfi, *params_used;
-    const double *mapping, *pmin, *pmax, *pmean, *pstd, *lin_w, *lin_m, *lin_s, *covinv, *center;
-};
-
-// td_cov: where the test-Gaussian tables (covinv, center: the tail of the
-// double table) live -- the LDS copy, or tab_d itself when not staged
-__device__ Tabs make_tabs(const DevCfg &c, const int *ti, const double *td, const double *td_cov = nullptr)
-{
-    const TabLayout &l = c.tl;
-    if (!td_cov) td_cov = td;
-    return Tabs{ti, ti + l.blk_n, ti + l.blk_nchanged, ti + l.blk_changed_off, ti + l.blk_map_off, ti + l.blk_R_off,
-                ti + l.changed, ti + l.pfi, ti + l.params_used, td + l.mapping, td + l.pmin, td + l.pmax,
-                td + l.pmean, td + l.pstd, td + l.lin_w, td + l.lin_m, td + l.lin_s, td_cov + l.covinv,
-                td_cov + l.center};
-}
-
-struct Walker {
-    Rng r;
-    Col<double> R, P, trial, vec;
-    Col<int> cyc, cyclp, blklp, itmp;
-    int fast_ix;
-    int defer = 0;    // leave the mapping product to the caller (block index in pend_b, vec filled)
-    int pend_b = -1;
-    int defer_rot = 0;   // leave a new rotation of a wide block to rot_kernel (block index in pend_rot)
-    int pend_rot = -1;
-    double r1 = 0.0;     // a one-parameter block's rotation, just drawn (R may live in HBM: no read-back)
-    int col_pre = 0;     // vec already holds the proposal's column of R (mh_body's pre_col)
-};
-
-__device__ int cyc_next(Walker &k, int which, int n, int base)
-{   // CyclicIndexRandomizer%Next, propose.f90:75-86 (RandIndices RandUtils.f90:93-108)
-    const int lp = k.cyclp[which] % n + 1;
-    k.cyclp[which] = lp;
-    if (lp == 1) {
-        if (n == 1) {
-            (void)ranmar(k.r);                      // ix = int(ranmar()*1)+1 = 1
-            k.cyc[base] = 1;
-        } else {
-            for (int i = 0; i < n; i++) k.itmp[i] = i + 1;
-            for (int i = 1; i <= n; i++) {
-                const int ix = (int)(ranmar(k.r) * (n + 1 - i)) + 1;
-                k.cyc[base + i - 1] = k.itmp[ix - 1];
-                k.itmp[ix - 1] = k.itmp[n + 1 - i - 1];
-            }
-        }
-    }
-    return k.cyc[base + lp - 1];
-}
-
-// Rows of R may live in HBM (blocks too big for the LDS image): every pass over
-// a row loads it RCH elements at a time, all in flight together, instead of one
-// dependent round trip per element.  The sums keep the reference's q order.
-static constexpr int RCH = 8;
-
-__device__ void rot_matrix(Walker &k, int off, int n)
-{   // RotMatrix propose.f90:88-102 -> RandRotationD RandUtils.f90:133-153
-    // element (j,i) (row j) of this block's R at R[off + j*n + i]
-    if (n > 1) {
-        for (int j = 0; j < n; j++) {
-            double norm;
-            for (;;) {
-                for (int i = 0; i < n; i++) k.vec[i] = gaussian1(k.r);
-                for (int i = 0; i < j; i++) {   // vec = vec - sum(vec*R(i,:))*R(i,:)
-                    const int base = off + i * n;
-                    double s = 0.0;
-                    for (int q0 = 0; q0 < n; q0 += RCH) {
-                        double rv[RCH], vv[RCH];
-#pragma unroll
-                        for (int u = 0; u < RCH; u++) {
-                            const int q = q0 + u;
-                            rv[u] = q < n ? k.R[base + q] : 0.0;
-                            vv[u] = q < n ? k.vec[q] : 0.0;
-                        }
-#pragma unroll
-                        for (int u = 0; u < RCH; u++)
-                            if (q0 + u < n) s += vv[u] * rv[u];
-                    }
-                    for (int q0 = 0; q0 < n; q0 += RCH) {
-                        double rv[RCH];
-#pragma unroll
-                        for (int u = 0; u < RCH; u++) rv[u] = q0 + u < n ? k.R[base + q0 + u] : 0.0;
-#pragma unroll
-                        for (int u = 0; u < RCH; u++)
-                            if (q0 + u < n) k.vec[q0 + u] = k.vec[q0 + u] - s * rv[u];
-                    }
-                }
-                norm = 0.0;
-                for (int q = 0; q < n; q++) norm += k.vec[q] * k.vec[q];
-                if (norm > 1e-3) break;
-            }
-            const double sn = sqrt(norm), rsn = 1.0 / sn;
-            for (int q = 0; q < n; q++) k.R[off + j * n + q] = div_rn(k.vec[q], sn, rsn);   // = vec(q) / sn
-        }
-    } else {
-        for (int i = 0; i < n * n; i++) k.R[off + i] = 0.0;
-        for (int i = 0; i < n; i++) {
-            k.r1 = (ranmar(k.r) - 0.5) >= 0.0 ? 1.0 : -1.0;
-            k.R[off + i * n + i] = k.r1;
-        }
-    }
-}
-
-// blocks this wide get their rotations from rot_kernel.  (Narrower ones stay
-// in the chain: config5_bk15_plik's 7-wide foreground block deferred measured
-// mh_kernel 34.2 -> 20.7 us plus rot_kernel 15.0 us a step, no gain.)
-static constexpr int ROT_DEFER_MIN = 8;
-
-__device__ void proposal_tail(const DevCfg &c, const Tabs &t, Walker &k, int b, int lp);
-__device__ void proposal_r(const DevCfg &c, const Tabs &t, Walker &k, int b, int n, double r1);
-
-__device__ __forceinline__ void block_proposal(const DevCfg &c, const Tabs &t, Walker &k, int bi /*1-based*/)
-{   // GetBlockProposal :247-254 -> ProposeVec :105-120 -> Propose_r :122-139 -> UpdateParams :142-149
-    const int b = bi - 1;
-    const int n = t.blk_n[b];
-    const int off = t.blk_R_off[b];
-    int lp = k.blklp[b];
-    if (lp % n == 0) {
-        if (k.defer_rot && n >= ROT_DEFER_MIN) {   // rot_kernel draws it and finishes this proposal
-            k.pend_rot = b;
-            return;
-        }
-        rot_matrix(k, off, n);
-        lp = 0;
-        if (n == 1) {   // a fresh one-parameter rotation every step: its sign is in hand
-            k.blklp[b] = 1;
-            proposal_r(c, t, k, b, 1, k.r1);
-            return;
-        }
-    }
-    proposal_tail(c, t, k, b, lp);
-}
-
-// ProposeVec after the rotation check: loop index, step length, UpdateParams
-__device__ void proposal_tail(const DevCfg &c, const Tabs &t, Walker &k, int b, int lp)
-{
-    const int n = t.blk_n[b];
-    const int off = t.blk_R_off[b];
-    lp++;
-    k.blklp[b] = lp;
-    // vec(q) = R(q, loopix) (the column of R is read once: R may live in HBM
-    // when it is too big to stage), scaled by Propose_r's step below
-    for (int q0 = 0; !k.col_pre && q0 < n; q0 += RCH) {
-        double rv[RCH];
-#pragma unroll
-        for (int u = 0; u < RCH; u++) rv[u] = q0 + u < n ? k.R[off + (q0 + u) * n + (lp - 1)] : 0.0;
-#pragma unroll
-        for (int u = 0; u < RCH; u++)
-            if (q0 + u < n) k.vec[q0 + u] = rv[u];
-    }
-    proposal_r(c, t, k, b, n, 0.0);
-}
-
-// Propose_r's step length and UpdateParams: vec *= r * wid (r1: the 1 x 1
-// rotation itself, when n == 1 and it was just drawn), P(changed) += mapping . vec
-__device__ void proposal_r(const DevCfg &c, const Tabs &t, Walker &k, int b, int n, double r1)
-{
-    double rf;
-    if (ranmar(k.r) < 0.33) {
-        rf = (double)randexp1(k.r);
-    } else {
-        const int m = n < 2 ? n : 2;
-        rf = 0.0;
-        for (int i = 0; i < m; i++) {
-            const double g = gaussian1(k.r);
-            rf += g * g;
-        }
-        rf = sqrt(rf / m);
-    }
-    const double scale = rf * c.propose_scale;
-    const int nc = t.blk_nchanged[b];
-    const double *M = t.mapping + t.blk_map_off[b];
-    const int *chg = t.changed + t.blk_changed_off[b];
-    if (r1 != 0.0) k.vec[0] = r1 * scale;
-    else
-        for (int q0 = 0; q0 < n; q0 += RCH) {   // RCH loads in flight
-            double v[RCH];
-#pragma unroll
-            for (int u = 0; u < RCH; u++) v[u] = k.vec[q0 + u < n ? q0 + u : 0];
-#pragma unroll
-            for (int u = 0; u < RCH; u++)
-                if (q0 + u < n) k.vec[q0 + u] = v[u] * scale;
-        }
-    if (k.defer) {
-        k.pend_b = b;
-        return;
-    }
-    for (int j = 0; j < nc; j++) {
-        double s = 0.0;
-        for (int q = 0; q < n; q++) s += M[j * n + q] * k.vec[q];
-        k.trial[chg[j]] += s;
-    }
-}
-
-__device__ __forceinline__ void proposal_fast(const DevCfg &c, const Tabs &t, Walker &k)
-{   // :283-289
-    const int q = cyc_next(k, 2, c.fast_n, c.all_n + c.slow_n);
-    block_proposal(c, t, k, t.pfi[c.slow_n + q - 1]);
-}
-
-__device__ __forceinline__ void proposal_slow(const DevCfg &c, const Tabs &t, Walker &k)
-{   // :275-281
-    const int q = cyc_next(k, 1, c.slow_n, c.all_n);
-    block_proposal(c, t, k, t.pfi[q - 1]);
-}
-
-__device__ __forceinline__ void proposal(const DevCfg &c, const Tabs &t, Walker &k)
-{   // GetProposal :257-273
-    if (k.fast_ix != 0) {
-        proposal_fast(c, t, k);
-        k.fast_ix--;
-    } else if (cyc_next(k, 0, c.all_n, 0) > c.slow_n) {
-        proposal_fast(c, t, k);
-        k.fast_ix = c.oversample_fast - 1;
-    } else {
-        proposal_slow(c, t, k);
-    }
-}
-
-// GetLogLike calclike.f90:136-151 with AddLikeTemp :82-94; likes[l] are the
-// data-likelihood terms at q (LogLikeWithTheorySet :374-387)
-// test_row(i): row i of covinv . (q - center) (TestLikelihoodFunction's inner sum)
-template <class Q>
-__device__ inline double test_row(const DevCfg &c, const Tabs &t, const Q &q, int i)
-{
-    const int n = c.n_used;
-    double s = 0.0;
-    for (int j = 0; j < n; j++) s += t.covinv[i * n + j] * (q[t.params_used[j]] - t.center[t.params_used[j]]);
-    return s;
-}
-
-// trows (stride MB), when given, holds (q - center)_i x test_row(i) for every
-// i, computed by the other waves of mh_kernel: the same products, summed here
-// in the same order (built with -ffp-contract=off: no fused multiply-add)
-// zrows / oobv (stride MB), when given, hold every parameter's squared prior z
-// (0 where there is no prior) and the bounds verdict of q, formed by the other
-// thread groups: the same terms, summed here in the same order
-template <class Q, class L>
-__device__ __forceinline__ double target_like(const DevCfg &c, const Tabs &t, const Q &q, const L &likes,
-                              const double *trows = nullptr, const double *zrows = nullptr, const int *oobv = nullptr)
-{
-    // the parameter loops load RCH entries at a time (all in flight together;
-    // the chain wave would otherwise wait out one LDS round trip per entry)
-    bool oob = oobv ? *oobv != 0 : false;
-    for (int i0 = 0; !oobv && i0 < c.np; i0 += RCH) {                // GetLogLikeBounds :97-109
-        double qv[RCH], hi[RCH], lo[RCH];
-#pragma unroll
-        for (int u = 0; u < RCH; u++) {
-            const int i = i0 + u < c.np ? i0 + u : 0;
-            qv[u] = q[i];
-            hi[u] = t.pmax[i];
-            lo[u] = t.pmin[i];
-        }
-#pragma unroll
-        for (int u = 0; u < RCH; u++)
-            if (i0 + u < c.np && (qv[u] > hi[u] || qv[u] < lo[u])) oob = true;
-    }
-    if (oob) return LOGZERO;
-    double main = 0.0;
-    if (c.test_like) {                                               // TestLikelihoodFunction :180-199
-        const int n = c.n_used;
-        double d = 0.0;
-        for (int i0 = 0; trows && i0 < n; i0 += RCH) {   // the products, formed by the thread groups
-            double v[RCH];
-#pragma unroll
-            for (int u = 0; u < RCH; u++) v[u] = trows[(size_t)(i0 + u < n ? i0 + u : 0) * MB];
-#pragma unroll
-            for (int u = 0; u < RCH; u++)
-                if (i0 + u < n) d += v[u];
-        }
-        for (int i = 0; !trows && i < n; i++)
-            d += (q[t.params_used[i]] - t.center[t.params_used[i]]) * test_row(c, t, q, i);
-        main = d / 2.0;
-    }
-    for (int l = 0; l < c.n_like; l++) {
-        const double v = likes[l];
-        if (v == LOGZERO) return LOGZERO;
-        main += v;
-    }
-    double like = main / c.temperature;
-    if (c.has_priors) {                                              // GetLogPriors :111-134
-        double pri = 0.0;
-        for (int i0 = 0; zrows && i0 < c.np; i0 += RCH) {
-            double zv[RCH];
-#pragma unroll
-            for (int u = 0; u < RCH; u++) zv[u] = zrows[(size_t)(i0 + u < c.np ? i0 + u : 0) * MB];
-#pragma unroll
-            for (int u = 0; u < RCH; u++)
-                if (i0 + u < c.np) pri += zv[u];
-        }
-        for (int i0 = 0; !zrows && i0 < c.np; i0 += RCH) {   // std already 0 where the varying/include_fixed gate (:119) is off
-            double qv[RCH], mu[RCH], sd[RCH];
-#pragma unroll
-            for (int u = 0; u < RCH; u++) {
-                const int i = i0 + u < c.np ? i0 + u : 0;
-                qv[u] = q[i];
-                mu[u] = t.pmean[i];
-                sd[u] = t.pstd[i];
-            }
-#pragma unroll
-            for (int u = 0; u < RCH; u++)
-                if (i0 + u < c.np && sd[u] != 0.0) {
-                    const double z = (qv[u] - mu[u]) / sd[u];
-                    pri += z * z;
-                }
-        }
-        for (int k = 0; k < c.n_lin; k++)    // linear combinations :125-131
-            if (t.lin_s[k] != 0.0) {
-                const double *wk = t.lin_w + (size_t)k * c.np;
-                double s = 0.0;
-                for (int i = 0; i < c.np; i++) s += wk[i] * q[i];
-                const double z = (s - t.lin_m[k]) / t.lin_s[k];
-                pri += z * z;
-            }
-        like = like + (pri / 2.0) / c.temperature;
-    }
-    return like;
-}
-
-// Phase timestamps (s_memtime) of the first 64 mh_kernel blocks, only in the
-// instrumented build (make EXTRA=-DCMAMD_STAMPS; tools/mh_stamps.py).
-#ifdef CMAMD_STAMPS
-__device__ unsigned long long g_stamps[64][16];
-#define STAMP(i)                                                                                \
-    do {                                                                                        \
-        const unsigned long long t_ = __builtin_amdgcn_s_memtime();                            \
-        if (ACCEPT && PROPOSE && lane == 0 && wave == 0 && blockIdx.x < 64) g_stamps[blockIdx.x][i] = t_;            \
-    } while (0)
-#else
-#define STAMP(i) ((void)0)
-#endif
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void gbl_void_t;
-
-// LDS-DMA (global_load_lds_dwordx4): rows [r0, r0+n) of a [rows][ld] double
-// array, columns wb..wb+MB-1, into LDS rows [d0, d0+n) of [row][MB].  One wave
-// instruction moves 1 KB (64 lanes x 16 bytes), i.e. 1024 / (8 MB) rows, and
-// nothing passes through VGPRs, so every piece of the walker state is in
-// flight at once.  Lanes past the last row are off.
-__device__ inline void dma_rows_f64(double *dst, int d0, const double *src, int r0, int n, size_t ld, int wb,
-                                    int lane, int wave = 0, int nw = 1)
-{
-    constexpr int LPR = MB / 2, RPI = 64 / LPR;   // lanes per row, rows per instruction
-    for (int r = RPI * wave; r < n; r += RPI * nw) {
-        const int rr = r + lane / LPR;
-        if (rr < n) {
-            const double *g = src + (size_t)(r0 + rr) * ld + wb + 2 * (lane % LPR);
-            __builtin_amdgcn_global_load_lds((gbl_void_t *)g, (lds_void_t *)(dst + (size_t)(d0 + r) * MB), 16, 0, 0);
-        }
-    }
-}
-
-// same for int rows
-__device__ inline void dma_rows_i32(int *dst, const int *src, int n, size_t ld, int wb, int lane, int wave = 0,
-                                    int nw = 1)
-{
-    constexpr int LPR = MB / 4, RPI = 64 / LPR;
-    for (int r = RPI * wave; r < n; r += RPI * nw) {
-        const int rr = r + lane / LPR;
-        if (rr < n) {
-            const int *g = src + (size_t)rr * ld + wb + 4 * (lane % LPR);
-            __builtin_amdgcn_global_load_lds((gbl_void_t *)g, (lds_void_t *)(dst + (size_t)r * MB), 16, 0, 0);
-        }
-    }
-}
-
-// flat copy of n 4-byte words (source allocation padded to a multiple of 64 words)
-__device__ inline void dma_words(void *dst, const void *src, int n, int lane, int wave = 0, int nw = 1)
-{
-    for (int i = 64 * wave; i < n; i += 64 * nw) {
-        const unsigned *g = reinterpret_cast<const unsigned *>(src) + i + lane;
-        __builtin_amdgcn_global_load_lds((gbl_void_t *)g, (lds_void_t *)(reinterpret_cast<unsigned *>(dst) + i), 4,
-                                         0, 0);
-    }
-}
-
-// write-back of LDS rows [row][MB] (src rows src_r0 + (r - r0)) to HBM rows r
-// in [r0, r1), columns wb .. wb+MB-1: 16 bytes per thread (MB = 16 doubles is 8
-// threads a row, 16 ints 4 threads), all threads of the block, rows round-robin
-template <class T>
-__device__ inline void stage_out(T *dst, const T *src, int src_r0, int r0, int r1, size_t ld, int wb)
-{
-    constexpr int PER = 16 / sizeof(T), TPR = MB / PER, RPB = MH_THREADS / TPR;   // per thread, threads per row, rows per pass
-    const int tr = threadIdx.x / TPR, col = (threadIdx.x % TPR) * PER;
-    for (int r = r0 + tr; r < r1; r += RPB)
-        *reinterpret_cast<uint4 *>(dst + (size_t)r * ld + wb + col) =
-            *reinterpret_cast<const uint4 *>(src + (size_t)(src_r0 + r - r0) * MB + col);
-}
-
-// changeMask of the trial (TheoryLike_GetLogLikeMain, calclike.f90:302-306):
-// likelihood l must be recomputed iff a parameter it depends on moved
-// (LogLikeWithTheorySet :377); 1 = recompute, 0 = keep the current term
-template <class QT, class QP>
-__device__ inline void write_like_flags(const DevCfg &c, const QT &trial, const QP &P, int w)
-{
-    for (int l = 0; l < c.n_like; l++) {
-        const unsigned long long m = c.like_dep[l];
-        bool ch = false;
-        for (int i = 0; i < c.np; i++)
-            if (((m >> i) & 1ull) && trial[i] != P[i]) ch = true;
-        c.like_flag[(size_t)l * c.ld + w] = ch ? 1 : 0;
-    }
-}
-
-// One launch per Metropolis step boundary: accept/reject the pending trial
-// (MetropolisAccept MCMC.f90:119-131 + MoveDone :166-190), then propose the
-// next trial (GetProposal / GetProposalFast) and scatter its nuisance
-// parameters for the likelihood kernels.  MB walkers per block.
-// A Metropolis workgroup of the unified step launch waits here until its
-// walker tile's quadratic-form and chi^2 workgroups have arrived (TailWait),
-// then acquires their write-through outputs.  The producers are all earlier in
-// the grid and wait on nothing, so the count arrives; the wait still gives up
-// after TAIL_WAIT_SPINS polls and sets the status word, which the next step
-// call reports as an error (sampler_check_pipe).  The bound counts polls, not
-// wall-clock time: a poll does not advance while the wave is switched out (a
-// shared GPU), so a waiter restored before its producers never gives up early.
-// The per-tile arrival counters each on a line of their own (TW_PAD words
-// apart), and the waiters poll them every TW_SLEEP x 64 cycles: the counters
-// are agent-scope, so every poll and arrival goes past the XCD's L2, and 64
-// waiters polling one line in a tight loop slow the quadratic form's own
-// loads on the chip.
-#ifndef CMAMD_TW_SLEEP
-#define CMAMD_TW_SLEEP 20
-#endif
-#ifndef CMAMD_TW_PAD
-#define CMAMD_TW_PAD 64
-#endif
-static constexpr int TW_PAD = CMAMD_TW_PAD;
-// walkers per chi^2 workgroup in the unified launch (4 / 8 / 16: 35.7-35.8 /
-// 35.9-36.0 / 35.9-36.0 us per middle launch, round 5)
-#ifndef CMAMD_UNI_WT
-#define CMAMD_UNI_WT 4
-#endif
-static constexpr int UNI_WT = CMAMD_UNI_WT;
-// the pass role's weight prefetch: one step ahead (0), or two as the standalone
-// kernels (1: measured 0.3 us slower a launch with 288-l items, and the same
-// within noise with 352-l items: 32.6 / 32.0 / 31.8 against 32.1 / 32.4 / 31.9 us, round 6)
-#ifndef CMAMD_UNI_W2
-#define CMAMD_UNI_W2 0
-#endif
-static constexpr long TAIL_WAIT_SPINS = (1l << 25) / CMAMD_TW_SLEEP;   // polls: ~1 s
-
-// A give-up: the sampler's status word lives in pinned host memory (mapped),
-// so the host reads it once the step call's event has completed, without a
-// copy launch; every writer stores the same bit, so a plain system-scope store
-// serves (no read-modify-write over the bus)
-__device__ __forceinline__ void pipe_giveup(int *status)
-{
-    __hip_atomic_store(status, CMBL_STATUS_PIPE_WAIT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-__device__ __forceinline__ void tail_wait(const TailWait &tw, int tile)
-{
-    if (threadIdx.x == 0) {
-        const int gpt = 64 / tw.gwt, g0 = tile * gpt;
-        const int gq = max(0, min(gpt, tw.ng - g0));
-        // every accepting launch adds its quadratic-form workgroups, and those whose
-        // chi^2 ran as workgroups of its own (not folded) add the tile's chi^2 ones
-        const unsigned target = tw.epoch * (unsigned)tw.nq_items + tw.epoch_g * (unsigned)gq;
-        for (long it = 0;; it++) {
-            const unsigned v = __hip_atomic_load(tw.cnt + tile * TW_PAD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (v >= target) break;
-            if (it == TAIL_WAIT_SPINS) {
-                pipe_giveup(tw.status);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(CMAMD_TW_SLEEP);
-        }
-        // one acquire after the match (cdna_hip_programming.md Guideline 16 recipe): it drops this
-        // CU's L1 lines; its own wait holds the barrier, then every wave loads
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef CMAMD_STAMPS
-        if (blockIdx.x < 2048) g_uni_stamps[tw.stamp_slot][blockIdx.x][1] = __builtin_amdgcn_s_memrealtime();
-#endif
-    }
-    __syncthreads();
-}
-
+#include "mhpropose.h"
+#include "mhstage.h"
+#include "mhwait.h"
 #include "mhlean.h"
 
-// tw: the unified step launch's wait (mh_step_kernel), else null
-template <bool ACCEPT, bool PROPOSE>
-__device__ __forceinline__ void mh_body(const DevCfg &c, int fast_only, double *hist_row, double *hist_terms, int blk0,
-                                        double *lds, int bx, const TailWait *tw = nullptr)
-{
-    if (c.lean.on) {   // a single one-parameter fast block (mhlean.h)
-        mh_lean<ACCEPT, PROPOSE>(c, hist_row, hist_terms, blk0, lds, bx, tw);
-        return;
-    }
-    const Rows &R = c.rows;
-    const int lane = threadIdx.x % MB, grp = threadIdx.x / MB;    // walker in block, thread group
-    const int wl64 = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = MH_THREADS / 64;
-    const int wb = (blk0 + bx) * MB;
-    const int w = wb + lane;
-    const bool act = w < c.W;
-    const size_t W = c.ld;
-    const int nlk = (c.n_like + 1) & ~1;
-    // LDS carve: state doubles | like terms | vec scratch | tables(d) | state ints | itmp | tables(i)
-    const int nd_st = c.stage_R ? R.ND : R.ND - R.RR;           // staged double rows
-    const int ni_st = c.stage_cyc ? R.NI : R.CYC;                // staged int rows
-    const int ntd = c.stage_cov ? c.tl.n_dbl : c.tl.covinv;      // staged double-table words
-    double *sd = lds;                                            // [nd_st][MB]
-    double *lk = sd + (size_t)nd_st * MB;                        // [nlk][MB]
-    double *vc = lk + (size_t)nlk * MB;                          // [max_blk][MB]
-    double *tq = vc + (size_t)c.max_blk * MB;                    // [tq_rows][MB] test-Gaussian row sums / block
-    double *dq = tq + (size_t)c.tq_rows * MB;                    // [def_cap][QF_GROUPS + 1][MB] deferred combines
-    double *td = dq + (size_t)c.def_cap * (QF_GROUPS + 1) * MB;  // [ntd rounded to 32]
-    int *si = reinterpret_cast<int *>(td + ((ntd + 31) & ~31));  // [ni_st][MB]
-    int *it = si + (size_t)ni_st * MB;                           // [all_n][MB] when stage_cyc
-    int *ti = it + (size_t)(c.stage_cyc ? c.all_n : 0) * MB;     // [n_int rounded to 64]
-    int *oobw = ti + ((c.tl.n_int + 63) & ~63);                  // [MB] trial out of bounds (par_prior)
-    double *zz = reinterpret_cast<double *>(oobw + MB);          // [np][MB] the trial's squared prior z (par_prior)
-    int *ndw = reinterpret_cast<int *>(zz + (size_t)c.np * MB);  // [MB] ring entries the chain's draws wrote
-    int *i0w = ndw + MB;                                         // [MB] the ring index before them
-    if (threadIdx.x < MB) oobw[threadIdx.x] = 0;
-    // the rotation list of this walker range: this launch appends to counter
-    // rot_par; the other one (read by the previous step's rot_kernel) restarts
-    if (PROPOSE && c.rot_defer && bx == 0 && threadIdx.x == 0)
-        c.rot_cnt[2 * (blk0 * MB / 64) + (c.rot_par ^ 1)] = 0;
-    const bool skipR = !c.stage_R;
-    // staged double row index of global row r (rotation rows dropped when not staged)
-#define SROW(r) ((skipR && (r) >= R.R) ? (r) - R.RR : (r))
-
-    STAMP(0);
-    // every wave issues the LDS-DMA of the state image; lanes 0..MB-1 of wave
-    // 0 alone run the chain logic; every thread group writes the image back
-    const int rEnd = R.R + R.RR;
-    if (skipR) {
-        dma_rows_f64(sd, 0, c.sd, 0, R.R, W, wb, wl64, wave, nwave);
-        dma_rows_f64(sd, R.R, c.sd, rEnd, R.ND - rEnd, W, wb, wl64, wave, nwave);
-    } else {
-        dma_rows_f64(sd, 0, c.sd, 0, R.ND, W, wb, wl64, wave, nwave);
-    }
-    dma_rows_i32(si, c.si, ni_st, W, wb, wl64, wave, nwave);
-    dma_words(td, c.tab_d, 2 * ntd, wl64, wave, nwave);
-    dma_words(ti, c.tab_i, c.tl.n_int, wl64, wave, nwave);
-    // fast-only proposals with R in HBM: the only fast block's next column
-    // (R(:, lp + 1) when no rotation is due) fetched into the vec rows by the
-    // thread groups (proposal_tail then skips its own read; a block that
-    // rotates writes R only in rot_kernel).  When the host knows the loop
-    // index (pre_lp) the loads go out here, beside the image; otherwise after
-    // it, from the staged index
-    const bool pre_col = PROPOSE && fast_only && !c.stage_R && c.pre_blk >= 0;
-    constexpr int NRQ = (MAXBLK + NV - 1) / NV;
-    double rq[NRQ];
-    int col = -1, ncol = 0;
-    const bool rq_early = pre_col && c.pre_lp >= 0;
-    if (rq_early && act) {
-        ncol = c.pre_n;
-        if (c.pre_lp % ncol != 0) col = c.pre_off + c.pre_lp;
-#pragma unroll
-        for (int u = 0; u < NRQ; u++) {
-            const int q = grp + u * NV;
-            if (col >= 0 && q < ncol) rq[u] = c.sd[(size_t)(R.R + col + q * ncol) * W + w];
-        }
-    }
-    if (tw) tail_wait(*tw, wb / 64);   // the trial's terms below come from this launch's producers
-    dma_rows_f64(lk, 0, c.like_terms, 0, nlk, W, wb, wl64, wave, nwave);
-    // per-likelihood terms of the current point, for the history (rejected walkers keep theirs)
-    double ct[MAXLIKE];
-    if (ACCEPT && hist_terms && grp == 0 && act) {
-#pragma unroll
-        for (int l = 0; l < MAXLIKE; l++)
-            if (l < c.n_like) ct[l] = c.cur_terms[(size_t)l * W + w];
-    }
-    // deferred split-K combines: the 16 group sums of this walker tile's
-    // partials, one group per wave, loaded beside the state image
-    if (ACCEPT && c.n_def) {   // group g sums split-K group g of this block's walkers (columns wb % 64 + lane of the tile)
-        const int tile = wb / QF_TILE, col = wb % QF_TILE + lane;
-        for (int d = 0; d < MAXDEF; d++) {
-            if (d >= c.n_def) break;
-            const double *tp = c.def_part[d] + (size_t)tile * c.def_items[d] * QF_TILE;
-            double *row = dq + (size_t)d * (QF_GROUPS + 1) * MB;
-            if (grp < QF_GROUPS) row[(size_t)grp * MB + lane] = qf_group_sum(tp, c.def_items[d], grp, col);
-            if (grp == NV - 1) row[(size_t)QF_GROUPS * MB + lane] = (c.def_add[d] && act) ? c.def_add[d][w] : 0.0;
-        }
-    }
-    STAMP(1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (ACCEPT && c.n_def && grp == 0 && act) {   // finish them in quadform.h's fixed order
-        for (int d = 0; d < MAXDEF; d++) {
-            if (d >= c.n_def) break;
-            const double *row = dq + (size_t)d * (QF_GROUPS + 1) * MB;
-            double v = qf_tree(row + lane, MB);
-            if (c.def_add[d]) v = v + row[(size_t)QF_GROUPS * MB + lane];
-            const int l = c.def_like[d];
-            lk[(size_t)l * MB + lane] = v;
-            const_cast<double *>(c.like_terms)[(size_t)l * W + w] = v;
-        }
-    }
-    // the test-Gaussian rows of covinv . (trial - center) are spread over the
-    // waves (each row summed by one thread, in order) instead of run serially
-    // by the chain wave: first the differences (trial - center)_j, one row
-    // each (tq rows n_used ..), then the rows' sums and their products with
-    // the differences (tq rows 0 ..), every sum's loads in flight together
-    const bool par_test = ACCEPT && c.test_like && c.n_used >= 4 && c.tq_rows >= 2 * c.n_used;
-    const bool par_map = PROPOSE && c.max_blk >= 4 && c.tq_rows >= 2;
-    // the trial's bounds check and squared Gaussian-prior z of every parameter,
-    // spread over the thread groups (the chain thread then only sums them in order)
-    const bool par_prior = ACCEPT;
-    if (par_test || par_prior || pre_col) {
-        if (pre_col && !rq_early && act) {
-            const int b = c.pre_blk, off = ti[c.tl.blk_R_off + b];
-            ncol = ti[c.tl.blk_n + b];
-            const int lp = si[(size_t)(R.BLKLP + b) * MB + lane];
-            if (lp % ncol != 0) col = off + lp;
-#pragma unroll
-            for (int u = 0; u < NRQ; u++) {
-                const int q = grp + u * NV;
-                if (col >= 0 && q < ncol) rq[u] = c.sd[(size_t)(R.R + col + q * ncol) * W + w];
-            }
-        }
-        const Tabs t0 = make_tabs(c, ti, td, c.stage_cov ? td : c.tab_d);
-        const Col<double> q{sd + (size_t)SROW(R.T) * MB + lane, MB};
-        const int nu = c.n_used;
-        double *dif = tq + (size_t)nu * MB + lane;
-        if (act) {
-            if (par_test)
-                for (int i = grp; i < nu; i += NV) {
-                    const int pi = t0.params_used[i];
-                    dif[(size_t)i * MB] = q[pi] - t0.center[pi];
-                }
-            if (par_prior) {
-                int oob = 0;
-                for (int i = grp; i < c.np; i += NV) {
-                    const double qv = q[i];
-                    if (qv > t0.pmax[i] || qv < t0.pmin[i]) oob = 1;   // GetLogLikeBounds :97-109
-                    double z2 = 0.0;
-                    if (c.has_priors && t0.pstd[i] != 0.0) {           // GetLogPriors :111-124
-                        const double z = (qv - t0.pmean[i]) / t0.pstd[i];
-                        z2 = z * z;
-                    }
-                    zz[(size_t)i * MB + lane] = z2;
-                }
-                if (oob) atomicOr(&oobw[lane], 1);
-            }
-        }
-        if (par_test) {
-            __syncthreads();
-            if (act)
-                for (int i = grp; i < nu; i += NV) {   // test_row's sum, same order
-                    const double *ci = t0.covinv + (size_t)i * nu;
-                    double s = 0.0;
-                    for (int j0 = 0; j0 < nu; j0 += RCH) {
-                        double cv[RCH], dv[RCH];
-#pragma unroll
-                        for (int u = 0; u < RCH; u++) {
-                            const int j = j0 + u < nu ? j0 + u : 0;
-                            cv[u] = ci[j];
-                            dv[u] = dif[(size_t)j * MB];
-                        }
-#pragma unroll
-                        for (int u = 0; u < RCH; u++)
-                            if (j0 + u < nu) s += cv[u] * dv[u];
-                    }
-                    tq[(size_t)i * MB + lane] = dif[(size_t)i * MB] * s;
-                }
-        }
-#pragma unroll
-        for (int u = 0; u < NRQ; u++) {
-            const int qq = grp + u * NV;
-            if (col >= 0 && qq < ncol) vc[(size_t)qq * MB + lane] = rq[u];
-        }
-        __syncthreads();
-    }
-    STAMP(2);
-    if (grp == 0 && act) {
-
-    const Tabs t = make_tabs(c, ti, td, c.stage_cov ? td : c.tab_d);
-    Walker k;
-    k.r.u = Col<double>{sd + (size_t)R.U * MB + lane, MB};
-    k.r.c = sd[(size_t)R.C * MB + lane];
-    k.r.gset = sd[(size_t)R.G * MB + lane];
-    k.r.i97 = si[(size_t)R.I97 * MB + lane];
-    k.r.j97 = si[(size_t)R.J97 * MB + lane];
-    k.r.iset = si[(size_t)R.ISET * MB + lane];
-    k.R = c.stage_R ? Col<double>{sd + (size_t)R.R * MB + lane, MB} : Col<double>{c.sd + (size_t)R.R * W + w, c.ld};
-    k.P = Col<double>{sd + (size_t)SROW(R.P) * MB + lane, MB};
-    k.trial = Col<double>{sd + (size_t)SROW(R.T) * MB + lane, MB};
-    k.vec = Col<double>{vc + lane, MB};
-    k.cyc = c.stage_cyc ? Col<int>{si + (size_t)R.CYC * MB + lane, MB} : Col<int>{c.si + (size_t)R.CYC * W + w, c.ld};
-    k.cyclp = Col<int>{si + (size_t)R.CYCLP * MB + lane, MB};
-    k.blklp = Col<int>{si + (size_t)R.BLKLP * MB + lane, MB};
-    k.itmp = c.stage_cyc ? Col<int>{it + lane, MB} : Col<int>{c.itmp_g + w, c.ld};
-    k.fast_ix = si[(size_t)R.FASTIX * MB + lane];
-    const int i97_0 = k.r.i97;
-    double &cur = sd[(size_t)SROW(R.L) * MB + lane];
-    double &mult = sd[(size_t)SROW(R.M) * MB + lane];
-    int &nacc = si[(size_t)R.NACC * MB + lane];
-
-    bool moved = false;   // accepted: P = trial already
-    if (ACCEPT) {
-        if (c.mask_on) {   // unchanged likelihoods keep the current point's term (calclike.f90:377-384)
-            for (int l = 0; l < c.n_like; l++) {
-                const int f = c.like_flag[(size_t)l * W + w];
-                double v;
-                if (f == 0) v = c.cur_terms[(size_t)l * W + w];
-                else if (c.like_out[l]) v = c.like_out[l][f - 1];        // sparse: compacted slot
-                else v = lk[(size_t)l * MB + lane];
-                lk[(size_t)l * MB + lane] = v;
-            }
-        }
-        STAMP(8);
-        const double like = target_like(c, t, k.trial, Col<double>{lk + lane, MB}, par_test ? tq + lane : nullptr,
-                                        par_prior ? zz + lane : nullptr, par_prior ? oobw + lane : nullptr);
-        STAMP(9);
-        bool acc = false;
-        if (like != LOGZERO) {
-            acc = cur > like;
-            if (!acc) acc = (double)randexp1(k.r) > like - cur;
-        }
-        STAMP(10);
-        moved = acc;
-        if (acc) {
-            if (mult > 0) nacc += 1;
-            mult = 1.0;
-            for (int i0 = 0; !par_map && i0 < c.np; i0 += RCH) {   // P = trial (par_map: the groups, below)
-                double v[RCH];
-#pragma unroll
-                for (int u = 0; u < RCH; u++) v[u] = k.trial[i0 + u < c.np ? i0 + u : 0];
-#pragma unroll
-                for (int u = 0; u < RCH; u++)
-                    if (i0 + u < c.np) k.P[i0 + u] = v[u];
-            }
-            cur = like;
-#pragma unroll
-            for (int l = 0; l < MAXLIKE; l++)
-                if (l < c.n_like) {
-                    ct[l] = lk[(size_t)l * MB + lane];
-                    c.cur_terms[(size_t)l * W + w] = ct[l];
-                }
-        } else {
-            mult += 1.0;
-        }
-        STAMP(11);
-        si[(size_t)R.ACCF * MB + lane] = acc ? 1 : 0;
-        if (par_map) oobw[lane] = acc ? 1 : 0;   // (target_like has read the bounds verdict)
-        if (hist_row) hist_row[(size_t)c.n_used * c.W + w] = cur;   // the parameters: every group, below
-        if (hist_terms) {
-#pragma unroll
-            for (int l = 0; l < MAXLIKE; l++)
-                if (l < c.n_like) hist_terms[(size_t)l * c.W + w] = ct[l];
-        }
-    }
-    STAMP(3);
-    if (PROPOSE) {
-        for (int i0 = 0; !moved && !par_map && i0 < c.np; i0 += RCH) {   // Trial = CurParams (par_map: below)
-            double v[RCH];
-#pragma unroll
-            for (int u = 0; u < RCH; u++) v[u] = k.P[i0 + u < c.np ? i0 + u : 0];
-#pragma unroll
-            for (int u = 0; u < RCH; u++)
-                if (i0 + u < c.np) k.trial[i0 + u] = v[u];
-        }
-        STAMP(14);
-        k.defer = par_map;
-        k.defer_rot = c.rot_defer;
-        k.col_pre = pre_col && k.blklp[c.pre_blk] % t.blk_n[c.pre_blk] != 0 &&
-                    (!rq_early || k.blklp[c.pre_blk] == c.pre_lp);   // else proposal_tail reads the column itself
-        if (fast_only) proposal_fast(c, t, k);
-        else proposal(c, t, k);
-        STAMP(15);
-        si[(size_t)R.PROT * MB + lane] = k.pend_rot + 1;             // rot_kernel finishes this walker
-        if (k.pend_rot >= 0) {
-            const int slot = atomicAdd(c.rot_cnt + 2 * (blk0 * MB / 64) + c.rot_par, 1);
-            c.rot_list[blk0 * MB + slot] = w;
-            if (par_map) tq[lane] = -1.0;
-        } else if (par_map) tq[lane] = (double)k.pend_b;             // the block, for the mapping waves
-        else {
-            for (int l = 0; l < c.n_like; l++)
-                for (int q = 0; q < c.like_nn[l]; q++)
-                    c.like_nuis[l][(size_t)w * c.like_nn[l] + q] = k.trial[t.ti[c.like_nidx[l] + q]];
-            if (c.mask_on) write_like_flags(c, k.trial, k.P, w);
-        }
-    }
-    STAMP(4);
-    sd[(size_t)R.C * MB + lane] = k.r.c;
-    sd[(size_t)R.G * MB + lane] = k.r.gset;
-    si[(size_t)R.I97 * MB + lane] = k.r.i97;
-    si[(size_t)R.J97 * MB + lane] = k.r.j97;
-    si[(size_t)R.ISET * MB + lane] = k.r.iset;
-    si[(size_t)R.FASTIX * MB + lane] = k.fast_ix;
-    ndw[lane] = k.r.nd < 97 ? k.r.nd : 97;
-    i0w[lane] = i97_0;
-    }
-    if (par_map) {   // UpdateParams' mapping product, rows spread over the waves (one thread per row, same order)
-        __syncthreads();
-        // first P = trial (accepted) or trial = P (rejected, or no accept in
-        // this launch: oobw is 0), the chain having left both to the groups
-        if (act) {
-            double *Pr = sd + (size_t)SROW(R.P) * MB + lane, *Tr = sd + (size_t)SROW(R.T) * MB + lane;
-            const bool mv = oobw[lane] != 0;
-            for (int i = grp; i < c.np; i += NV) {
-                if (mv) Pr[(size_t)i * MB] = Tr[(size_t)i * MB];
-                else Tr[(size_t)i * MB] = Pr[(size_t)i * MB];
-            }
-        }
-        __syncthreads();
-        if (act && tq[lane] >= 0.0) {
-            const Tabs t = make_tabs(c, ti, td, c.stage_cov ? td : c.tab_d);
-            const int b = (int)tq[lane];
-            const int n = t.blk_n[b], nc = t.blk_nchanged[b];
-            const double *M = t.mapping + t.blk_map_off[b];
-            const int *chg = t.changed + t.blk_changed_off[b];
-            double *trial = sd + (size_t)SROW(R.T) * MB + lane;
-            const double *vec = vc + lane;
-            for (int j = grp; j < nc; j += NV) {
-                double s = 0.0;
-#pragma unroll 4
-                for (int q = 0; q < n; q++) s += M[j * n + q] * vec[(size_t)q * MB];
-                trial[(size_t)chg[j] * MB] += s;
-            }
-        }
-        __syncthreads();
-        STAMP(12);
-        if (grp == 0 && act && si[(size_t)R.PROT * MB + lane] == 0) {
-            const double *trial = sd + (size_t)SROW(R.T) * MB + lane;
-            for (int l = 0; l < c.n_like; l++)
-                for (int q = 0; q < c.like_nn[l]; q++)
-                    c.like_nuis[l][(size_t)w * c.like_nn[l] + q] = trial[(size_t)ti[c.like_nidx[l] + q] * MB];
-            if (c.mask_on)
-                write_like_flags(c, Col<const double>{trial, MB}, Col<const double>{sd + (size_t)SROW(R.P) * MB + lane, MB},
-                                 w);
-        }
-    }
-    __syncthreads();
-    STAMP(13);
-    if (ACCEPT && hist_row && act) {   // the history row's parameters (P is final), rows spread over the groups
-        const int *pu = ti + c.tl.params_used;
-        for (int i = grp; i < c.n_used; i += NV)
-            hist_row[(size_t)i * c.W + w] = sd[(size_t)(SROW(R.P) + pu[i]) * MB + lane];
-    }
-    if (PROPOSE && c.pub_on && threadIdx.x < MB && act)   // the fused pass / bins in this launch poll for these
-        for (int k = 0; k < 2; k++) {
-            const int pc = c.pub_pcal[k];
-            const bool rp = si[(size_t)R.PROT * MB + lane] != 0;   // rot_kernel proposes it (bin co-run only)
-            const double v = rp ? __longlong_as_double((long long)TP_PIPE_ROT)
-                                : pc >= 0 ? sd[(size_t)(SROW(R.T) + pc) * MB + lane] : 1.0;
-            __hip_atomic_store(c.calbuf + (size_t)k * W + w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(c.calbuf_next + (size_t)k * W + w, __longlong_as_double((long long)TP_PIPE_UNSET),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // read by the next launch only
-        }
-    // write back the image (rows of walkers past W are padding of the ld-wide
-    // rows: written back unchanged) -- of the RANMAR ring only the entries
-    // this launch's draws overwrote (positions i97 - 1, i97 - 2, ... mod 97
-    // of the first index)
-    if (act) {
-        const int nd = ndw[lane], i0 = i0w[lane];
-        for (int t = grp; t < nd; t += NV) {
-            int p = i0 - 1 - t;
-            if (p < 0) p += 97;
-            c.sd[(size_t)(R.U + p) * W + w] = sd[(size_t)(R.U + p) * MB + lane];
-        }
-    }
-    if (skipR) {
-        stage_out(c.sd, sd, R.C, R.C, R.R, W, wb);
-        stage_out(c.sd, sd, R.R, rEnd, R.ND, W, wb);
-    } else {
-        stage_out(c.sd, sd, R.C, R.C, R.ND, W, wb);
-    }
-    stage_out(c.si, si, 0, 0, ni_st, W, wb);
-    STAMP(5);
-#ifdef CMAMD_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    STAMP(6);
-#endif
-#undef SROW
-}
+#include "mhbody.h"
 
 template <bool ACCEPT, bool PROPOSE>
 __global__ __launch_bounds__(MH_THREADS) void mh_kernel(DevCfg c, int fast_only, double *hist_row, double *hist_terms, int blk0)
@@ -1120,107 +185,7 @@ __global__ __launch_bounds__(MH_THREADS) void mh_bin_kernel(DevCfg c, int fast_o
         }
 }
 
-// The unified step launch (pipe_mode 3): one launch per fast step.  Rows of
-// workgroups (tail_rows) run step k's tails -- plik_lite's quadratic form from
-// raw sums and the lensing chi^2, which store write-through and arrive on
-// their walker tile's counter -- the window pass storing step k + 1's raw sums,
-// and last the Metropolis workgroups, which wait for their tile's arrivals
-// (tail_wait), accept step k (finishing plik's deferred combine from the
-// partials of this launch) and propose step k + 1.  The pass waits on
-// nothing; the Metropolis chain of a tile starts as soon as its tails are
-// done instead of at a kernel boundary, and overlaps the pass.
-// The hand-off is cdna_hip_programming.md's counter recipe in its
-// write-through form (the note to its split-K combine, after Guideline 16):
-// the producers' stores are sc1 (write-through past the XCD L2), so no
-// release fence precedes the relaxed agent-scope fetch_add -- every wave
-// drains its stores, the workgroup barriers, one lane adds; the consumer
-// polls relaxed and takes one acquire fence after the match (tail_wait).
-// A release fence here would be a whole-L2 write-back per producer
-// workgroup (measured on the pass units: 35.8 -> 122 us a launch).
-__device__ __forceinline__ void tail_arrive(const TailWait &tw, int tile)
-{
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's write-through stores are done
-    __syncthreads();
-    if (threadIdx.x == 0 && !tw.nosignal)
-        __hip_atomic_fetch_add(tw.cnt + tile * TW_PAD, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-template <bool ACCEPT, bool PROPOSE>
-__device__ __forceinline__ void mh_step_body(DevCfg &c, int fast_only, double *hist_row, double *hist_terms,
-                                             StepTail &t, const int2 *__restrict__ rows, TailWait &tw, int nmh)
-{
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    const int2 rr = rows[blockIdx.x >> 3];
-    const int lb = rr.y * 8 + (blockIdx.x & 7);
-    if (!ACCEPT && blockIdx.x == 0)   // a call's first launch (no tails): the arrival counters start from 0
-        for (int i = threadIdx.x; i < tw.ntiles; i += MH_THREADS) tw.cnt[i] = 0u;
-#ifdef CMAMD_STAMPS
-    const bool stamp = ACCEPT && threadIdx.x == 0 && blockIdx.x < 2048;
-    const int slot = PROPOSE ? 0 : 1;
-    if (stamp) {
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        g_uni_stamps[slot][blockIdx.x][0] = __builtin_amdgcn_s_memrealtime();
-        g_uni_stamps[slot][blockIdx.x][2] = xcc & 15;
-        g_uni_stamps[slot][blockIdx.x][4] = 0;
-        g_uni_stamps[slot][blockIdx.x][5] = 0;
-    }
-    struct End {
-        bool on;
-        int role, slot;
-        __device__ ~End() {
-            if (on) {
-                g_uni_stamps[slot][blockIdx.x][3] = __builtin_amdgcn_s_memrealtime();
-                g_uni_stamps[slot][blockIdx.x][4] = role + 1;
-            }
-        }
-    } end_{stamp, rr.x, slot};
-#endif
-    if (rr.x == TAIL_QF) {
-        if (lb >= t.nq) return;
-        int item_ix, tile;
-        qf_place(lb, t.q.src.n_items, t.q.src.xcd_map, item_ix, tile);
-        // the quadratic form's waves above the pass's at issue (the Metropolis
-        // waves' 3 stays highest): 35.98 / 36.26 -> 35.90 / 35.80 us per step in two
-        // interleaved repetitions (round 6, tools/gpu_r6f.sh); CMAMD_QF_PRIO=0 turns it off
-        if (t.qf_prio) __builtin_amdgcn_s_setprio(2);
-        if (PROPOSE && t.qf_ahead)   // A/B (CMAMD_QF_AHEAD): the two-step-ahead form in the middle launches too
-            qfs_body<true, true>(lds, item_ix, tile, t.q);
-        else
-            qfs_body<true, !PROPOSE>(lds, item_ix, tile, t.q);
-        tail_arrive(tw, tile);
-    } else if (rr.x == TAIL_GAUSS) {
-        // contiguous walker groups per XCD (lb % 8 is the XCD): each partial row's
-        // 128-byte lines are read by one XCD's L2 instead of four (35.1 -> 34.5 us)
-        const int grows = (t.ng + 7) >> 3, q = (lb & 7) * grows + (lb >> 3);
-        if (q >= t.ng) return;
-        small_gauss_body<UNI_WT, true, true>(t.g, lds, q);
-        tail_arrive(tw, q * UNI_WT / 64);
-    } else if (rr.x == TAIL_PASS) {
-        if (lb >= t.np) return;
-        tp_vec_body<2, true, CMAMD_UNI_W2 != 0>(t.tp, t.dl, t.ld_field, t.ld_walker, t.W, reinterpret_cast<char *>(lds), lb);
-    } else if (lb < nmh) {
-        // the chain is latency on one lane: its waves, dispatched last (the youngest,
-        // so the last in issue arbitration), take the SIMD first (34.6 -> 34.0 us)
-        if (!t.fold_late_prio) __builtin_amdgcn_s_setprio(3);
-        if (ACCEPT && t.fold_g) {
-            // the small chi^2 of this workgroup's 16 walkers (step k's raw partial
-            // rows, whole 128-byte lines) while the quadratic form runs elsewhere:
-            // nX <= 16, so its sums are those of the 4-walker rows (same bits); the
-            // chain's loads of the term follow tail_wait's acquire
-            if (t.fold_tpf == 2) small_gauss_body<MB, true, false, 2>(t.g, lds, lb);
-            else small_gauss_body<MB, true, false, 1>(t.g, lds, lb);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-#ifdef CMAMD_STAMPS
-            if (threadIdx.x == 0 && blockIdx.x < 2048)
-                g_uni_stamps[PROPOSE ? 0 : 1][blockIdx.x][5] = __builtin_amdgcn_s_memrealtime();
-#endif
-        }
-        if (t.fold_late_prio) __builtin_amdgcn_s_setprio(3);   // A/B: the folded chi^2 at the default priority
-        mh_body<ACCEPT, PROPOSE>(c, fast_only, hist_row, hist_terms, 0, lds, lb, ACCEPT ? &tw : nullptr);
-    }
-}
+#include "mhstep.h"
 
 template <bool ACCEPT, bool PROPOSE>
 __global__ __launch_bounds__(MH_THREADS, 3) void mh_step_kernel(DevCfg c, int fast_only, double *hist_row,
@@ -1241,826 +206,8 @@ __global__ __launch_bounds__(MH_THREADS, 3) void mh_tail_kernel(DevCfg c, int fa
     mh_step_body<ACCEPT, PROPOSE>(c, fast_only, hist_row, hist_terms, t, rows, tw, nmh);
 }
 
-// ------------------------------------------------------- deferred rotations
-// A new random rotation of a block of ROT_DEFER_MIN or more parameters
-// (RotMatrix propose.f90:88-102 -> RandRotationD RandUtils.f90:133-153) is too
-// big for the chain lane: mh_kernel stops that walker's proposal at the
-// rotation (Rows::PROT), appends the walker to the step's rotation list, and
-// rot_kernel, one wave per listed walker, finishes it.
-//
-// The Gaussians.  RANMAR's lagged-Fibonacci part is x_m = x_{m-97} - x_{m-33}
-// mod 1 (RandUtils.f90:350-374), an integer recurrence mod 2^24 in units of
-// 2^-24, and its carry c_m = c - (m+1) cd mod cm has a closed form, so the 64
-// lanes make 64 uniforms per round (lanes 33..63 substitute x_{m-33} =
-// x_{m-130} - x_{m-66}).  The lanes then take Gaussian1's polar pairs
-// (uniforms 2p, 2p+1, RandUtils.f90:156-178) 32 at a time, and the accepted
-// pairs are placed by a ballot prefix in stream order (v2 fac, then the saved
-// deviate v1 fac).  Nothing is committed until the rotation is done; then the
-// state advances by exactly the uniforms the consumed Gaussians used (ring,
-// i97/j97, c, iset, gset): bit-identical to drawing them one at a time.
-//
-// Gram-Schmidt.  Lane j owns row j's vec in registers.  Row i is final once
-// its projections on rows 0..i-1 are done, so the rows advance in lockstep:
-// at iteration i lane i takes its norm (below 1e-3 row i is redrawn and the
-// later rows restart on the shifted Gaussians) and publishes R(i,:) in LDS,
-// then every lane j > i projects onto it.  Every sum runs over q in order, as
-// the reference's sum() and rot_matrix do, so R is bit-identical.  A rotation
-// whose Gaussians would overflow the LDS buffers (many redraws) is redone by
-// the serial path (lane 0 draws, the lanes project with readlane sums), which
-// is also the debug reference (DevCfg::rot_serial).
-
-// sum of x over lanes 0..n-1 in lane order, formed identically on every lane
-// from v_readlane broadcasts (no LDS round trip, no divergent lane-0 section)
-__device__ __forceinline__ double lane_sum_ordered(double x, int n)
-{
-    const long long bits = __double_as_longlong(x);
-    const int lo = (int)bits, hi = (int)(bits >> 32);
-    double s = 0.0;
-#pragma unroll
-    for (int q = 0; q < MAXBLK; q++)
-        if (q < n) {
-            const unsigned l = (unsigned)__builtin_amdgcn_readlane(lo, q);
-            const long long h = __builtin_amdgcn_readlane(hi, q);
-            s += __longlong_as_double((h << 32) | l);
-        }
-    return s;
-}
-
-__device__ __forceinline__ double readlane_f64(double x, int q)
-{
-    const long long bits = __double_as_longlong(x);
-    const unsigned l = (unsigned)__builtin_amdgcn_readlane((int)bits, q);
-    const long long h = __builtin_amdgcn_readlane((int)(bits >> 32), q);
-    return __longlong_as_double((h << 32) | l);
-}
-
-// LDS written by some lanes of a wave and read by others (the wave's LDS
-// operations complete in order; this keeps the compiler from moving them)
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-static constexpr int ROT_WAVES = 4;                        // walkers per rot_kernel workgroup (a wave each)
-static constexpr int ROT_GC = MAXBLK * (MAXBLK + 4);       // Gaussians a parallel rotation may use (>= n (n + ROT_SPEC))
-static constexpr int ROT_GA = ROT_GC + 128;                // + one pair round's overshoot
-static constexpr int ROT_UC = 1536;                        // uniforms (a multiple of 64)
-
-struct RotLds {
-    double g[ROT_GA];             // the Gaussian stream from the rotation's start (g[0] = gset if iset)
-    double rm[MAXBLK * MAXBLK];   // R(i, q) at rm[i * MAXBLK + q]
-    double u[98];                 // RANMAR u(1:97) as doubles (the state rows' form)
-    double gs[MAXBLK];            // serial path: one attempt's Gaussians
-    int x[ROT_UC];                // lagged-Fibonacci values x_m (units of 2^-24)
-    int o[ROT_UC];                // uniforms x_m - c_m (units of 2^-24)
-    int pi[ROT_GA / 2];           // pair index of the r-th accepted pair
-    int ui[100];                  // u(1:97) in units of 2^-24
-};
-
-struct RotGen {
-    int i97, j97, C0;             // RANMAR pointers and carry (units of 2^-24) at the start
-    int off;                      // 1 when the start state holds a saved deviate (iset)
-    int m = 0, p = 0, nr = 0;     // uniforms made, pairs taken, pairs accepted
-    int cbase;                    // carry before this round's first call: C0 - m cd mod cm
-    int ck;                       // this lane's (lane + 1) cd mod cm
-};
-
-__device__ __forceinline__ int mod97(int v) { return v >= 97 ? v - 97 : v; }   // v in [0, 194)
-
-__device__ __forceinline__ int rot_x(const RotLds &L, const RotGen &G, int p)
-{   // x_p; p in [-97, -1] is the start ring: u(i97 - 1 - p mod 97)
-    return p >= 0 ? L.x[p] : L.ui[mod97(G.i97 - 1 - p)];
-}
-
-__device__ __forceinline__ int sub24(int a, int b) { const int d = a - b; return d < 0 ? d + (1 << 24) : d; }
-
-static constexpr int RM_P = 16777213, RM_CD = 7654321;     // cm and cd in units of 2^-24
-
-__device__ void rot_uniforms(RotLds &L, RotGen &G, int lane)
-{   // 64 uniforms
-    const int m = G.m + lane;
-    const int b = lane < 33 ? rot_x(L, G, m - 33) : sub24(rot_x(L, G, m - 130), rot_x(L, G, m - 66));
-    const int x = sub24(rot_x(L, G, m - 97), b);
-    int cm = G.cbase - G.ck;                 // c after call m: C0 - (m + 1) cd mod cm
-    if (cm < 0) cm += RM_P;
-    L.x[m] = x;
-    L.o[m] = sub24(x, cm);
-    G.m += 64;
-    G.cbase -= (64 * RM_CD) % RM_P;
-    if (G.cbase < 0) G.cbase += RM_P;
-    wave_sync();
-}
-
-__device__ void rot_pairs(RotLds &L, RotGen &G, int lane)
-{   // up to 64 polar pairs of the uniforms made so far
-    const int p = G.p + lane;
-    bool acc = false;
-    double v1 = 0.0, v2 = 0.0, rr = 0.0;
-    if (2 * p < G.m) {
-        v1 = 2.0 * ((double)L.o[2 * p] * (1.0 / 16777216.0)) - 1.0;
-        v2 = 2.0 * ((double)L.o[2 * p + 1] * (1.0 / 16777216.0)) - 1.0;
-        rr = v1 * v1 + v2 * v2;
-        acc = rr < 1.0;
-    }
-    const unsigned long long mask = __ballot(acc);
-    if (acc) {
-        const int r = G.nr + __popcll(mask & ((1ull << lane) - 1ull));
-        const double fac = sqrt(-2.0 * log(rr) / rr);
-        L.g[G.off + 2 * r] = v2 * fac;
-        L.g[G.off + 2 * r + 1] = v1 * fac;
-        L.pi[r] = p;
-    }
-    G.nr += __popcll(mask);
-    G.p = min(G.p + 64, G.m / 2);
-    wave_sync();
-}
-
-// Gaussians g[0, need): the uniforms for about 1.3 pairs per missing
-// accepted pair go first (their rounds are short), then the pairs 64 at a time
-__device__ __forceinline__ bool rot_fill(RotLds &L, RotGen &G, int need, int lane)
-{
-    if (need > ROT_GC) return false;
-    while (G.off + 2 * G.nr < need) {
-        const int short_pairs = (need - G.off - 2 * G.nr + 1) / 2;
-        int want = 2 * (G.p + short_pairs + short_pairs / 3 + 8);
-        want = min(ROT_UC, (want + 63) & ~63);
-        if (want <= G.m) {
-            if (2 * G.p < G.m) want = G.m;        // pairs left to take
-            else if (G.m + 64 <= ROT_UC) want = G.m + 64;
-            else return false;                    // the uniform buffer is spent
-        }
-        while (G.m < want) rot_uniforms(L, G, lane);
-        while (2 * G.p < G.m && G.off + 2 * G.nr < need) rot_pairs(L, G, lane);
-    }
-    return true;
-}
-
-// advance the RANMAR / Gaussian1 state past the first T Gaussians of the stream
-__device__ void rot_commit(RotLds &L, const RotGen &G, int T, Rng &r, int lane)
-{
-    const int t = T - G.off;
-    int K = 0;
-    if (t > 0) {
-        const int q = (t - 1) / 2;            // the pair that gave the last Gaussian
-        K = 2 * (L.pi[q] + 1);
-        r.iset = t & 1;
-        r.gset = L.g[G.off + 2 * q + 1];
-    } else {
-        r.iset = 0;
-    }
-    for (int s = lane; s < 97; s += 64) {    // ring slot s (u(s+1)) last written by call m = i97-1-s mod 97 (+97k)
-        const int r0 = mod97(G.i97 - 1 - s + 97);
-        if (K - 1 >= r0) L.ui[s] = L.x[r0 + 97 * ((K - 1 - r0) / 97)];
-        L.u[s] = (double)L.ui[s] * (1.0 / 16777216.0);
-    }
-    r.i97 = (G.i97 - 1 - K % 97 + 97) % 97 + 1;
-    r.j97 = (G.j97 - 1 - K % 97 + 97) % 97 + 1;
-    int cm = G.C0 - (int)((long long)K * RM_CD % RM_P);
-    if (cm < 0) cm += RM_P;
-    r.c = (double)cm * (1.0 / 16777216.0);
-    wave_sync();
-}
-
-#ifdef CMAMD_STAMPS
-__device__ unsigned long long g_rot_ticks[3];     // first listed walker: total, Gaussian draws, Gram-Schmidt
-#define RTICK(v) (v) = __builtin_amdgcn_s_memtime()
-#else
-#define RTICK(v) ((void)0)
-#endif
-
-static constexpr int ROT_SPEC = 2;   // idle lanes n, n+1 carry the last row's next two attempts
-
-// One lockstep Gram-Schmidt pass over rows start..n-1 (row j from the n
-// Gaussians at g[gbase + (j - start) n]); NQ = n rounded up to 8.  The
-// padding columns q in [n, NQ) hold +0.0 in vec and in R, so every product
-// there is +0.0 and the sums (which start at +0.0) are bit-identical to sums
-// over q < n, with no selects.  Lane i publishes its raw vec and the lanes
-// divide one element each.  A redraw is most likely for the last row (its
-// residual has one degree of freedom: P(norm <= 1e-3) = 2.5 %), so lanes n and
-// n+1 project the Gaussians that follow as that row's second and third
-// attempts and stand in when it fails.  Returns -1 and the last row's extra
-// attempts in *extra, or the row to redraw and its failed attempts in *extra.
-template <int NQ>
-__device__ int rot_gs_pass(RotLds &L, int n, int start, int gbase, int lane, int spec, int *extra)
-{
-    const int top = n + spec;
-    double v[NQ], pp[NQ];
-    if (lane >= start && lane < top) {
-        const double *gv = L.g + gbase + (lane - start) * n;   // within g: the fill covered (top - start) n
-#pragma unroll
-        for (int q = 0; q < NQ; q++) {
-            const double x = gv[q];
-            v[q] = q < n ? x : 0.0;
-        }
-    }
-    for (int i = 0; i < n; i++) {
-        if (i >= start) {
-            const bool last = i == n - 1;
-            double norm = 0.0;
-            if (lane == i || (last && lane >= n && lane < top)) {
-#pragma unroll
-                for (int q = 0; q < NQ; q++) pp[q] = v[q] * v[q];
-#pragma unroll
-                for (int q = 0; q < NQ; q++) norm += pp[q];
-            }
-            int src = i, a = 0;
-            double nv = readlane_f64(norm, i);
-            if (!(nv > 1e-3)) {               // RandRotationD :143: draw row i again
-                if (!last) {
-                    *extra = 1;
-                    return i;
-                }
-                for (a = 1; a <= spec; a++) {
-                    nv = readlane_f64(norm, n - 1 + a);
-                    if (nv > 1e-3) break;
-                }
-                if (a > spec) {
-                    *extra = 1 + spec;
-                    return i;
-                }
-                src = n - 1 + a;
-            }
-            *extra = a;
-            double *ri = L.rm + i * MAXBLK;
-            if (lane == src)
-#pragma unroll
-                for (int q = 0; q < NQ; q += 2) *reinterpret_cast<double2 *>(ri + q) = make_double2(v[q], v[q + 1]);
-            wave_sync();
-            if (lane < NQ) {                  // R(i, q) = vec(q) / sqrt(norm), lane q
-                const double x = ri[lane];
-                ri[lane] = lane < n ? x / sqrt(nv) : 0.0;
-            }
-            wave_sync();
-        }
-        if (i < n - 1 && lane > i && lane < top) {   // vec = vec - sum(vec*R(i,:))*R(i,:)
-            const double *ri = L.rm + i * MAXBLK;
-            double rv[NQ];
-#pragma unroll
-            for (int q = 0; q < NQ; q += 2) {
-                const double2 t = *reinterpret_cast<const double2 *>(ri + q);
-                rv[q] = t.x;
-                rv[q + 1] = t.y;
-            }
-#pragma unroll
-            for (int q = 0; q < NQ; q++) pp[q] = v[q] * rv[q];
-            double s = 0.0;
-#pragma unroll
-            for (int q = 0; q < NQ; q++) s += pp[q];
-#pragma unroll
-            for (int q = 0; q < NQ; q++) pp[q] = s * rv[q];
-#pragma unroll
-            for (int q = 0; q < NQ; q++) v[q] = v[q] - pp[q];
-        }
-    }
-    return -1;
-}
-
-// the parallel rotation into L.rm; false (state untouched) when the buffers overflow
-__device__ bool rot_parallel(RotLds &L, Rng &r, int n, int lane, int spec, unsigned long long *tk)
-{
-    RotGen G;
-    G.i97 = r.i97;
-    G.j97 = r.j97;
-    G.C0 = (int)(r.c * 16777216.0);
-    G.off = r.iset ? 1 : 0;
-    G.cbase = G.C0;
-    G.ck = (lane + 1) * RM_CD % RM_P;                      // < 64 cd < 2^31
-    if ((G.i97 - G.j97 + 97) % 97 != 64) return false;     // not RMARIN's pointer pair: serial path
-    for (int s = lane; s < 97; s += 64) L.ui[s] = (int)(L.u[s] * 16777216.0);
-    if (lane == 0 && G.off) L.g[0] = r.gset;
-    wave_sync();
-    int start = 0, gbase = 0;
-    (void)tk;
-    for (;;) {                                // one pass per redraw
-#ifdef CMAMD_STAMPS
-        unsigned long long t0, t1;
-        RTICK(t0);
-#endif
-        if (!rot_fill(L, G, gbase + (n - start + spec) * n, lane)) return false;
-#ifdef CMAMD_STAMPS
-        RTICK(t1);
-        tk[1] += t1 - t0;
-#endif
-        int extra = 0;
-        const int fail = n <= 8    ? rot_gs_pass<8>(L, n, start, gbase, lane, spec, &extra)
-                         : n <= 16 ? rot_gs_pass<16>(L, n, start, gbase, lane, spec, &extra)
-                         : n <= 24 ? rot_gs_pass<24>(L, n, start, gbase, lane, spec, &extra)
-                                   : rot_gs_pass<32>(L, n, start, gbase, lane, spec, &extra);
-        static_assert(MAXBLK == 32, "rot_gs_pass widths");
-#ifdef CMAMD_STAMPS
-        RTICK(t0);
-        tk[2] += t0 - t1;
-#endif
-        if (fail < 0) {
-            rot_commit(L, G, gbase + (n - start + extra) * n, r, lane);
-            return true;
-        }
-        gbase += (fail - start + extra) * n;
-        start = fail;
-    }
-}
-
-// the serial rotation into L.rm: lane 0 draws each attempt's Gaussians, lane q
-// holds column q of R, every sum is formed in q order from readlane broadcasts
-__device__ void rot_serial(RotLds &L, Rng &r, int n, int lane)
-{
-    double rcol[MAXBLK];
-#pragma unroll
-    for (int i = 0; i < MAXBLK; i++) rcol[i] = 0.0;
-    for (int j = 0; j < n; j++) {
-        double v, norm;
-        for (;;) {
-            if (lane == 0)
-                for (int q = 0; q < n; q++) L.gs[q] = gaussian1(r);
-            wave_sync();
-            v = lane < n ? L.gs[lane] : 0.0;
-#pragma unroll
-            for (int i = 0; i < MAXBLK; i++) {
-                if (i < j) {
-                    const double s = lane_sum_ordered(v * rcol[i], n);
-                    v = v - s * rcol[i];
-                }
-            }
-            norm = lane_sum_ordered(v * v, n);
-            wave_sync();
-            if (norm > 1e-3) break;
-        }
-        const double rv = v / sqrt(norm);
-#pragma unroll
-        for (int i = 0; i < MAXBLK; i++)
-            if (i == j) rcol[i] = rv;
-        if (lane < n) L.rm[j * MAXBLK + lane] = rv;
-    }
-    // lane 0's RNG state is the walker's: broadcast it
-    r.c = readlane_f64(r.c, 0);
-    r.gset = readlane_f64(r.gset, 0);
-    r.i97 = __builtin_amdgcn_readlane(r.i97, 0);
-    r.j97 = __builtin_amdgcn_readlane(r.j97, 0);
-    r.iset = __builtin_amdgcn_readlane(r.iset, 0);
-    wave_sync();
-}
-
-// One wave: walker w's pending rotation, then the rest of its proposal.
-__device__ void rot_walker(const DevCfg &c, int w, int lane, RotLds &L, bool stamp)
-{
-    const size_t ld = c.ld;
-    const Rows &R = c.rows;
-    const int b = c.si[(size_t)R.PROT * ld + w] - 1;
-    const Tabs t = make_tabs(c, c.tab_i, c.tab_d, c.tab_d);
-    const int n = t.blk_n[b], off = t.blk_R_off[b];
-    for (int i = lane; i < 97; i += 64) L.u[i] = c.sd[(size_t)(R.U + i) * ld + w];
-    Walker k;
-    k.r.u = Col<double>{L.u, 1};
-    k.r.c = c.sd[(size_t)R.C * ld + w];
-    k.r.gset = c.sd[(size_t)R.G * ld + w];
-    k.r.i97 = c.si[(size_t)R.I97 * ld + w];
-    k.r.j97 = c.si[(size_t)R.J97 * ld + w];
-    k.r.iset = c.si[(size_t)R.ISET * ld + w];
-    wave_sync();
-    unsigned long long tk[3] = {0, 0, 0};
-#ifdef CMAMD_STAMPS
-    RTICK(tk[0]);
-#endif
-    if (c.rot_serial == 1 || !rot_parallel(L, k.r, n, lane, c.rot_serial == 2 ? 0 : ROT_SPEC, tk))
-        rot_serial(L, k.r, n, lane);
-#ifdef CMAMD_STAMPS
-    if (stamp && lane == 0) {
-        g_rot_ticks[0] = __builtin_amdgcn_s_memtime() - tk[0];
-        g_rot_ticks[1] = tk[1];
-        g_rot_ticks[2] = tk[2];
-    }
-#else
-    (void)stamp;
-#endif
-    // R(i, q) (rm, row stride MAXBLK) -> the state rows and a packed copy (row stride n) in g
-    for (int e = lane; e < n * n; e += 64) {
-        const double x = L.rm[(e / n) * MAXBLK + e % n];
-        c.sd[(size_t)(R.R + off + e) * ld + w] = x;
-        L.g[e] = x;
-    }
-    wave_sync();
-    k.trial = Col<double>{c.sd + (size_t)R.T * ld + w, (int)ld};
-    k.P = Col<double>{c.sd + (size_t)R.P * ld + w, (int)ld};
-    if (lane == 0) {   // the rest of ProposeVec on column 1 of the packed copy of R, up to UpdateParams
-        k.R = Col<double>{L.g - off, 1};
-        k.vec = Col<double>{L.gs, 1};
-        k.blklp = Col<int>{c.si + (size_t)R.BLKLP * ld + w, (int)ld};
-        k.defer = 1;
-        proposal_tail(c, t, k, b, 0);
-    }
-    wave_sync();
-    {   // UpdateParams (propose.f90:142-149): one lane per changed parameter, each sum in q order
-        const int nc = t.blk_nchanged[b];
-        const double *M = t.mapping + t.blk_map_off[b];
-        const int *chg = t.changed + t.blk_changed_off[b];
-        for (int j = lane; j < nc; j += 64) {
-            double s = 0.0;
-            for (int q = 0; q < n; q++) s += M[j * n + q] * L.gs[q];
-            k.trial[chg[j]] += s;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // the trial row's stores, before lane 0 reads it
-    __builtin_amdgcn_wave_barrier();
-    double calr = 0.0;   // bin co-run: plik's trial calibration
-    if (lane == 0) {
-        for (int l = 0; l < c.n_like; l++)
-            for (int q = 0; q < c.like_nn[l]; q++)
-                c.like_nuis[l][(size_t)w * c.like_nn[l] + q] = k.trial[t.ti[c.like_nidx[l] + q]];
-        if (c.bin_on) calr = k.trial[t.ti[c.like_nidx[0] + c.bin_cal]];
-        if (c.mask_on) write_like_flags(c, k.trial, k.P, w);
-        c.sd[(size_t)R.C * ld + w] = k.r.c;
-        c.sd[(size_t)R.G * ld + w] = k.r.gset;
-        c.si[(size_t)R.I97 * ld + w] = k.r.i97;
-        c.si[(size_t)R.J97 * ld + w] = k.r.j97;
-        c.si[(size_t)R.ISET * ld + w] = k.r.iset;
-        c.si[(size_t)R.PROT * ld + w] = 0;
-    }
-    wave_sync();
-    for (int i = lane; i < 97; i += 64) c.sd[(size_t)(R.U + i) * ld + w] = L.u[i];
-    if (c.bin_on) {   // the walker's Delta rows from the bin co-run's raw sums (plik_bin_emit's operations)
-        const double cl = __shfl(calr, 0), c2 = cl * cl;
-        const size_t r = (size_t)w * c.bin_Np;
-#pragma unroll 4
-        for (int i = lane; i < c.bin_nused; i += 64) c.bin_delta[r + i] = c.bin_X[i] - c.bin_S[r + i] / c2;
-    }
-}
-
-// One wave per listed walker (the launch's list counter is wave-uniform).
-__global__ __launch_bounds__(64 * ROT_WAVES) void rot_kernel(DevCfg c, int g0)
-{
-    extern __shared__ __attribute__((aligned(16))) double rot_lds[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int idx = blockIdx.x * ROT_WAVES + wave;
-    if (idx >= c.rot_cnt[2 * (g0 / 64) + c.rot_par]) return;
-    rot_walker(c, c.rot_list[g0 + idx], lane, reinterpret_cast<RotLds *>(rot_lds)[wave], idx == 0);
-}
-
-#ifdef CMAMD_STAMPS
-extern "C" int cmamd_debug_rot_ticks(unsigned long long *host) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_rot_ticks), sizeof(g_rot_ticks)) == hipSuccess ? 0 : -5;
-}
-#endif
-
-// ---------------------------------------------------------------- fast dragging
-// TFastDraggingSampler_GetNewSample (MCMC.f90:338-452) in four launch stages,
-// one thread per walker on the walker state in HBM (the drag scratch lives in
-// separate rows, DragCfg::dd / di, so the Metropolis kernel's LDS image is
-// unchanged).  Between stages the host evaluates the likelihoods:
-//   set 1 at the trial-end rows T on the END slow point's theory,
-//   set 2 at the trial-start rows T2 on the walker's current theory.
-//   stage 0  TrialEnd = Cur + GetProposalSlow                        (:367-368)
-//   stage 1  CurEndLike; abort on logZero (:370-374); first delta    (:386-394)
-//   stage 2  interpolated Metropolis on (start, end) likes, sums; next delta,
-//            or (last step) the drag accept + MoveDone                (:395-452)
-// dst: 0 idle, 1 dragging, 2 aborted, 3 skipped (CurLike == logZero),
-//      4 accepted (the walker's theory must become the end theory)
-struct DragCfg {
-    double *dd;      // [3 np + 4 + max_blk + n_like][ld]: CE, CS, T2, (cel, csl, ss, se), vec scratch,
-                     //   per-likelihood terms at CE
-    int *di;         // [1 + all_n][ld]: dst, RandIndices scratch
-    int interp, istep;
-    const double *like_terms2;            // [n_like][ld] at T2
-    double *like_nuis2[MAXLIKE];          // [W][nn] DataParams at T2
-};
-
-// One walker's part of a drag stage (TFastDraggingSampler_GetNewSample,
-// MCMC.f90:338-452) on views of its state: in HBM (drag_kernel) or in an LDS
-// image (drag_staged_kernel).  STAGE 0 proposes the slow trial, 1 scores the
-// end point, 2 runs interpolation step g.istep.
-struct DragView {
-    Col<double> T, CE, CS, T2, ET, lk1, lk2;
-    double *cur, *mult, *cel, *csl, *ss, *se;
-    int *nacc, *dst;
-};
-
-template <int STAGE>
-__device__ __forceinline__ void drag_logic(const DevCfg &c, const DragCfg &g, const Tabs &t, Walker &k,
-                                           const DragView &v, int w, double *hist_row, double *hist_terms)
-{
-    const size_t ld = c.ld;
-    const int np = c.np;
-    const Col<double> T = v.T, CE = v.CE, CS = v.CS, T2 = v.T2, ET = v.ET, lk1 = v.lk1, lk2 = v.lk2;
-    double &cur = *v.cur;
-    double &mult = *v.mult;
-    int &nacc = *v.nacc;
-    double &cel = *v.cel;
-    double &csl = *v.csl;
-    double &ss = *v.ss;
-    double &se = *v.se;
-    int &dst = *v.dst;
-    auto keep_end_terms = [&]() {
-        for (int l = 0; l < c.n_like; l++) ET[l] = lk1[l];
-    };
-
-    auto scatter = [&]() {            // DataParams of both trial points
-        for (int l = 0; l < c.n_like; l++)
-            for (int q = 0; q < c.like_nn[l]; q++) {
-                c.like_nuis[l][(size_t)w * c.like_nn[l] + q] = T[t.ti[c.like_nidx[l] + q]];
-                g.like_nuis2[l][(size_t)w * c.like_nn[l] + q] = T2[t.ti[c.like_nidx[l] + q]];
-            }
-    };
-    auto next_delta = [&]() {         // GetProposalFastDelta (propose.f90:291-298) on both ends
-        Col<double> keep = k.trial;
-        for (int i = 0; i < np; i++) T2[i] = 0.0;
-        k.trial = T2;
-        proposal_fast(c, t, k);
-        k.trial = keep;
-        for (int i = 0; i < np; i++) {
-            const double d = T2[i];
-            T[i] = CE[i] + d;
-            T2[i] = CS[i] + d;
-        }
-    };
-    auto metropolis = [&](double like, double curl) {   // MCMC.f90:119-131
-        if (like == LOGZERO) return false;
-        bool a = curl > like;
-        if (!a) a = (double)randexp1(k.r) > like - curl;
-        return a;
-    };
-
-    if (STAGE == 0) {
-        if (cur == LOGZERO) {
-            dst = 3;
-        } else {
-            dst = 1;
-            for (int i = 0; i < np; i++) {
-                T[i] = k.P[i];
-                CS[i] = k.P[i];
-                T2[i] = k.P[i];
-            }
-            csl = cur;
-            proposal_slow(c, t, k);
-        }
-        scatter();
-    } else if (STAGE == 1) {
-        if (dst == 1) {
-            cel = target_like(c, t, T, lk1);
-            if (cel == LOGZERO) {
-                dst = 2;
-                mult += 1.0;
-            } else {
-                for (int i = 0; i < np; i++) CE[i] = T[i];
-                keep_end_terms();
-                ss = csl;
-                se = cel;
-                next_delta();
-            }
-        }
-        scatter();
-    } else {
-        if (dst == 1) {
-            const double el = target_like(c, t, T, lk1);
-            bool acc = el != LOGZERO;
-            double sl = 0.0;
-            if (acc) {
-                sl = target_like(c, t, T2, lk2);
-                acc = sl != LOGZERO;
-                if (acc) {
-                    const double frac = (double)g.istep / g.interp;
-                    const double cint = csl * (1 - frac) + frac * cel;
-                    const double ilike = sl * (1 - frac) + frac * el;
-                    acc = metropolis(ilike, cint);
-                }
-            }
-            if (acc) {
-                for (int i = 0; i < np; i++) {
-                    CE[i] = T[i];
-                    CS[i] = T2[i];
-                }
-                cel = el;
-                csl = sl;
-                keep_end_terms();
-            }
-            ss = ss + csl;
-            se = se + cel;
-            if (g.istep < g.interp - 1) {
-                next_delta();
-            } else {
-                const double cur_drag = ss / g.interp, drag = se / g.interp;
-                if (metropolis(drag, cur_drag)) {        // MoveDone :166-190 + :437-445
-                    if (mult > 0) nacc += 1;
-                    mult = 1.0;
-                    for (int i = 0; i < np; i++) k.P[i] = CE[i];
-                    cur = cel;
-                    for (int l = 0; l < c.n_like; l++) c.cur_terms[(size_t)l * ld + w] = ET[l];
-                    dst = 4;
-                } else {
-                    mult += 1.0;
-                    dst = 0;
-                }
-            }
-        }
-        if (g.istep < g.interp - 1) {
-            scatter();
-        } else {
-            if (dst == 2 || dst == 3) dst = 0;
-            if (hist_row)
-            {
-                for (int i = 0; i < c.n_used; i++) hist_row[(size_t)i * c.W + w] = k.P[t.params_used[i]];
-                hist_row[(size_t)c.n_used * c.W + w] = cur;
-            }
-            if (hist_terms)
-                for (int l = 0; l < c.n_like; l++) hist_terms[(size_t)l * c.W + w] = c.cur_terms[(size_t)l * ld + w];
-        }
-    }
-}
-
-template <int STAGE>
-__global__ __launch_bounds__(64) void drag_kernel(DevCfg c, DragCfg g, double *hist_row, double *hist_terms)
-{
-    const int w = blockIdx.x * 64 + threadIdx.x;
-    if (w >= c.W) return;
-    const size_t ld = c.ld;
-    const Rows &R = c.rows;
-    const int np = c.np;
-    auto drow = [&](double *b, int r) { return Col<double>{b + (size_t)r * ld + w, (int)ld}; };
-    auto irow = [&](int *b, int r) { return Col<int>{b + (size_t)r * ld + w, (int)ld}; };
-    const Tabs t = make_tabs(c, c.tab_i, c.tab_d);
-    Walker k;
-    k.r.u = drow(c.sd, R.U);
-    k.r.c = c.sd[(size_t)R.C * ld + w];
-    k.r.gset = c.sd[(size_t)R.G * ld + w];
-    k.r.i97 = c.si[(size_t)R.I97 * ld + w];
-    k.r.j97 = c.si[(size_t)R.J97 * ld + w];
-    k.r.iset = c.si[(size_t)R.ISET * ld + w];
-    k.R = drow(c.sd, R.R);
-    k.P = drow(c.sd, R.P);
-    k.trial = drow(c.sd, R.T);
-    k.vec = drow(g.dd, 3 * np + 4);
-    k.cyc = irow(c.si, R.CYC);
-    k.cyclp = irow(c.si, R.CYCLP);
-    k.blklp = irow(c.si, R.BLKLP);
-    k.itmp = irow(g.di, 1);
-    k.fast_ix = c.si[(size_t)R.FASTIX * ld + w];
-    DragView v;
-    v.T = k.trial;
-    v.CE = drow(g.dd, 0);
-    v.CS = drow(g.dd, np);
-    v.T2 = drow(g.dd, 2 * np);
-    v.ET = drow(g.dd, 3 * np + 4 + c.max_blk);   // terms at CE
-    v.lk1 = Col<double>{const_cast<double *>(c.like_terms) + w, (int)ld};
-    v.lk2 = Col<double>{const_cast<double *>(g.like_terms2) + w, (int)ld};
-    v.cur = c.sd + (size_t)R.L * ld + w;
-    v.mult = c.sd + (size_t)R.M * ld + w;
-    v.nacc = c.si + (size_t)R.NACC * ld + w;
-    v.cel = g.dd + (size_t)(3 * np + 0) * ld + w;
-    v.csl = g.dd + (size_t)(3 * np + 1) * ld + w;
-    v.ss = g.dd + (size_t)(3 * np + 2) * ld + w;
-    v.se = g.dd + (size_t)(3 * np + 3) * ld + w;
-    v.dst = g.di + w;
-    drag_logic<STAGE>(c, g, t, k, v, w, hist_row, hist_terms);
-    c.sd[(size_t)R.C * ld + w] = k.r.c;
-    c.sd[(size_t)R.G * ld + w] = k.r.gset;
-    c.si[(size_t)R.I97 * ld + w] = k.r.i97;
-    c.si[(size_t)R.J97 * ld + w] = k.r.j97;
-    c.si[(size_t)R.ISET * ld + w] = k.r.iset;
-    c.si[(size_t)R.FASTIX * ld + w] = k.fast_ix;
-}
-
-// The same stage on an LDS image of MB walkers' state (mh_kernel's staging:
-// the sampler rows, the drag rows, both likelihood-term sets and the tables by
-// LDS-DMA, one wait), so the chain's dependent reads are LDS round trips
-// instead of HBM ones; then the image is written back.  Used when the image
-// fits (drag_lds_bytes).
-__host__ __device__ inline int drag_rows(const DevCfg &c) { return 3 * c.np + 4 + c.max_blk + c.n_like; }
-
-template <int STAGE>
-__global__ __launch_bounds__(MH_THREADS) void drag_staged_kernel(DevCfg c, DragCfg g, double *hist_row,
-                                                                 double *hist_terms)
-{
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    const Rows &R = c.rows;
-    const int lane = threadIdx.x % MB;
-    const int wl64 = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = MH_THREADS / 64;
-    const int wb = blockIdx.x * MB;
-    const int w = wb + lane;
-    const size_t W = c.ld;
-    const int np = c.np;
-    const int nlk = (c.n_like + 1) & ~1;            // LDS rows (even); nl, nr of them are moved
-    const int nl = c.n_like;
-    const int nr = drag_rows(c);
-    const int ndd = (nr + 1) & ~1;
-    const int nd_st = c.stage_R ? R.ND : R.ND - R.RR;
-    const int ni_st = c.stage_cyc ? R.NI : R.CYC;
-    const int ntd = c.stage_cov ? c.tl.n_dbl : c.tl.covinv;
-    const bool skipR = !c.stage_R;
-    double *sd = lds;                                        // [nd_st][MB]
-    double *dd = sd + (size_t)nd_st * MB;                    // [ndd][MB] drag rows
-    double *l1 = dd + (size_t)ndd * MB;                      // [nlk][MB] terms at T
-    double *l2 = l1 + (size_t)nlk * MB;                      // [nlk][MB] terms at T2
-    double *td = l2 + (size_t)nlk * MB;                      // [ntd rounded to 32]
-    int *si = reinterpret_cast<int *>(td + ((ntd + 31) & ~31));   // [ni_st][MB]
-    int *dst_l = si + (size_t)ni_st * MB;                    // [4][MB] dst (row 0)
-    int *it = dst_l + 4 * MB;                                // [all_n][MB] RandIndices scratch
-    int *ti = it + (size_t)c.all_n * MB;                     // [n_int rounded to 64]
-#define SROW(r) ((skipR && (r) >= R.R) ? (r) - R.RR : (r))
-    const int rEnd = R.R + R.RR;
-    if (skipR) {
-        dma_rows_f64(sd, 0, c.sd, 0, R.R, W, wb, wl64, wave, nwave);
-        dma_rows_f64(sd, R.R, c.sd, rEnd, R.ND - rEnd, W, wb, wl64, wave, nwave);
-    } else {
-        dma_rows_f64(sd, 0, c.sd, 0, R.ND, W, wb, wl64, wave, nwave);
-    }
-    dma_rows_f64(dd, 0, g.dd, 0, nr, W, wb, wl64, wave, nwave);
-    dma_rows_f64(l1, 0, c.like_terms, 0, nl, W, wb, wl64, wave, nwave);
-    dma_rows_f64(l2, 0, g.like_terms2, 0, nl, W, wb, wl64, wave, nwave);
-    dma_rows_i32(si, c.si, ni_st, W, wb, wl64, wave, nwave);
-    dma_rows_i32(dst_l, g.di, 1, W, wb, wl64, wave, nwave);
-    dma_words(td, c.tab_d, 2 * ntd, wl64, wave, nwave);
-    dma_words(ti, c.tab_i, c.tl.n_int, wl64, wave, nwave);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x < MB && w < c.W) {
-        const Tabs t = make_tabs(c, ti, td, c.stage_cov ? td : c.tab_d);
-        auto lrow = [&](double *b, int r) { return Col<double>{b + (size_t)r * MB + lane, MB}; };
-        Walker k;
-        k.r.u = lrow(sd, R.U);
-        k.r.c = sd[(size_t)R.C * MB + lane];
-        k.r.gset = sd[(size_t)R.G * MB + lane];
-        k.r.i97 = si[(size_t)R.I97 * MB + lane];
-        k.r.j97 = si[(size_t)R.J97 * MB + lane];
-        k.r.iset = si[(size_t)R.ISET * MB + lane];
-        k.R = c.stage_R ? lrow(sd, R.R) : Col<double>{c.sd + (size_t)R.R * W + w, c.ld};
-        k.P = lrow(sd, SROW(R.P));
-        k.trial = lrow(sd, SROW(R.T));
-        k.vec = lrow(dd, 3 * np + 4);
-        k.cyc = c.stage_cyc ? Col<int>{si + (size_t)R.CYC * MB + lane, MB} : Col<int>{c.si + (size_t)R.CYC * W + w, c.ld};
-        k.cyclp = Col<int>{si + (size_t)R.CYCLP * MB + lane, MB};
-        k.blklp = Col<int>{si + (size_t)R.BLKLP * MB + lane, MB};
-        k.itmp = Col<int>{it + lane, MB};
-        k.fast_ix = si[(size_t)R.FASTIX * MB + lane];
-        DragView v;
-        v.T = k.trial;
-        v.CE = lrow(dd, 0);
-        v.CS = lrow(dd, np);
-        v.T2 = lrow(dd, 2 * np);
-        v.ET = lrow(dd, 3 * np + 4 + c.max_blk);
-        v.lk1 = lrow(l1, 0);
-        v.lk2 = lrow(l2, 0);
-        v.cur = sd + (size_t)SROW(R.L) * MB + lane;
-        v.mult = sd + (size_t)SROW(R.M) * MB + lane;
-        v.nacc = si + (size_t)R.NACC * MB + lane;
-        v.cel = dd + (size_t)(3 * np + 0) * MB + lane;
-        v.csl = dd + (size_t)(3 * np + 1) * MB + lane;
-        v.ss = dd + (size_t)(3 * np + 2) * MB + lane;
-        v.se = dd + (size_t)(3 * np + 3) * MB + lane;
-        v.dst = dst_l + lane;
-        const int i97_0 = k.r.i97;
-        drag_logic<STAGE>(c, g, t, k, v, w, hist_row, hist_terms);
-        dst_l[MB + lane] = k.r.nd < 97 ? k.r.nd : 97;   // rows 1, 2: the ring entries the draws overwrote
-        dst_l[2 * MB + lane] = i97_0;
-        sd[(size_t)R.C * MB + lane] = k.r.c;
-        sd[(size_t)R.G * MB + lane] = k.r.gset;
-        si[(size_t)R.I97 * MB + lane] = k.r.i97;
-        si[(size_t)R.J97 * MB + lane] = k.r.j97;
-        si[(size_t)R.ISET * MB + lane] = k.r.iset;
-        si[(size_t)R.FASTIX * MB + lane] = k.fast_ix;
-    }
-    __syncthreads();
-    // of the RANMAR ring only the entries this stage's draws overwrote
-    // (positions i97 - 1, i97 - 2, ... mod 97 of the first index), as mh_body:
-    // the stages 63.4-63.8 against 63.8-67.4 us a drag step (round 6, tools/gpu_r6u.sh)
-    if (w < c.W) {
-        const int nd = dst_l[MB + lane], i0 = dst_l[2 * MB + lane];
-        for (int q = threadIdx.x / MB; q < nd; q += NV) {
-            int p = i0 - 1 - q;
-            if (p < 0) p += 97;
-            c.sd[(size_t)(R.U + p) * W + w] = sd[(size_t)(R.U + p) * MB + lane];
-        }
-    }
-    if (skipR) {
-        stage_out(c.sd, sd, R.C, R.C, R.R, W, wb);
-        stage_out(c.sd, sd, R.R, rEnd, R.ND, W, wb);
-    } else {
-        stage_out(c.sd, sd, R.C, R.C, R.ND, W, wb);
-    }
-    stage_out(g.dd, dd, 0, 0, nr, W, wb);
-    stage_out(c.si, si, 0, 0, ni_st, W, wb);
-    stage_out(g.di, dst_l, 0, 0, 1, W, wb);
-#undef SROW
-}
-
-// accepted moves: the trial (end) slow point's theory becomes the walker's theory
-// (flag[w] == value: drag_kernel dst 4, or the Metropolis accept flag row)
-__global__ void drag_swap_theory(const int *flag, int value, int W, const double *src, long long src_ld,
-                                 double *dstth, long long dst_ld, long long n)
-{
-    const int w = blockIdx.y;
-    if (w >= W || flag[w] != value) return;
-    const double *a = src + (long long)w * src_ld;
-    double *d = dstth + (long long)w * dst_ld;
-    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
-    if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(d)) & 15) == 0) {   // 16-byte moves
-        const long long n2 = n / 2;
-        for (long long i = t; i < n2; i += stride)
-            reinterpret_cast<double2 *>(d)[i] = reinterpret_cast<const double2 *>(a)[i];
-        if (t == 0 && (n & 1)) d[n - 1] = a[n - 1];
-    } else {
-        for (long long i = t; i < n; i += stride) d[i] = a[i];
-    }
-}
+#include "mhrot.h"
+#include "mhdrag.h"
 
 // Starting point: -lnL of P = trial (likelihood terms already evaluated)
 __global__ void start_kernel(DevCfg c)
@@ -2137,138 +284,6 @@ __global__ __launch_bounds__(256) void gather_theory_kernel(const double *__rest
     const double *src = dl + (long long)map[w] * ld_walker;
     double *dst = dlc + (long long)w * ld_walker;
     for (long long i = threadIdx.x; i < ext; i += 256) dst[i] = src[i];
-}
-
-// Per-chain mean and covariance over history rows first..last
-// (SampleCollector.f90:235-246), two passes like the reference (mean, then
-// the centred products).  A block owns 64 walkers (lane = walker, coalesced
-// rows) and HS_PH row phases (wave p takes rows first+p, first+p+HS_PH, ...);
-// the phase partials are combined in fixed order, so results are
-// deterministic.  The covariance pass runs one block per (walker tile,
-// parameter i) with the n products of row i in registers (NC = n rounded up).
-static constexpr int HS_PH = 4;
-
-template <int NC>
-__global__ __launch_bounds__(64 * HS_PH) void hist_mean_kernel(const double *hist, int cap, int W, int n, int first,
-                                                              int last, double *means)
-{
-    __shared__ double part[HS_PH][NC][64];
-    const int lane = threadIdx.x & 63, ph = threadIdx.x >> 6;
-    const int w = blockIdx.x * 64 + lane;
-    double acc[NC];
-#pragma unroll
-    for (int j = 0; j < NC; j++) acc[j] = 0.0;
-    if (w < W)
-        for (int tt = first + ph; tt <= last; tt += HS_PH) {
-            const double *row = hist + (size_t)(tt % cap) * (n + 1) * W + w;
-#pragma unroll
-            for (int j = 0; j < NC; j++)
-                if (j < n) acc[j] += row[(size_t)j * W];
-        }
-#pragma unroll
-    for (int j = 0; j < NC; j++) part[ph][j][lane] = acc[j];
-    __syncthreads();
-    if (ph == 0 && w < W) {
-        const double cnt = last - first + 1;
-        for (int j = 0; j < n; j++) {
-            double v = part[0][j][lane];
-            for (int p = 1; p < HS_PH; p++) v += part[p][j][lane];
-            means[(size_t)w * n + j] = v / cnt;
-        }
-    }
-}
-
-template <int NC>
-__global__ __launch_bounds__(64 * HS_PH) void hist_cov_kernel(const double *hist, int cap, int W, int n, int first,
-                                                             int last, const double *means, double *covs)
-{
-    __shared__ double part[HS_PH][NC][64];
-    const int lane = threadIdx.x & 63, ph = threadIdx.x >> 6;
-    const int w = blockIdx.x * 64 + lane, i = blockIdx.y;
-    double acc[NC], m[NC];
-#pragma unroll
-    for (int j = 0; j < NC; j++) {
-        acc[j] = 0.0;
-        m[j] = (w < W && j < n) ? means[(size_t)w * n + j] : 0.0;
-    }
-    double mi = 0.0;
-#pragma unroll
-    for (int j = 0; j < NC; j++)
-        if (j == i) mi = m[j];
-    if (w < W)
-        for (int tt = first + ph; tt <= last; tt += HS_PH) {
-            const double *row = hist + (size_t)(tt % cap) * (n + 1) * W + w;
-            const double di = row[(size_t)i * W] - mi;
-#pragma unroll
-            for (int j = 0; j < NC; j++)
-                if (j < n) acc[j] += (row[(size_t)j * W] - m[j]) * di;
-        }
-#pragma unroll
-    for (int j = 0; j < NC; j++) part[ph][j][lane] = acc[j];
-    __syncthreads();
-    if (ph == 0 && w < W) {
-        const double cnt = last - first + 1;
-        for (int j = 0; j < n; j++) {
-            double v = part[0][j][lane];
-            for (int p = 1; p < HS_PH; p++) v += part[p][j][lane];
-            covs[(size_t)w * n * n + (size_t)i * n + j] = v / cnt;
-        }
-    }
-}
-
-// Per-GPU partial sums of the chain moments for the convergence exchange
-// (TMpiChainCollector_UpdateCovAndCheckConverge, SampleCollector.f90:233-286):
-// every walker is one chain with count = last-first+1 samples.
-//   gmean == nullptr : out = [S0 = sum count, sum count*m (n), sum count*cov (n*n),
-//                             sum cov (n*n), number of chains]
-//   gmean != nullptr : out = sum count*(m-gmean)(m-gmean)^T (n*n)
-// One block; each thread owns a fixed strided set of walkers and the partials
-// are combined in a fixed tree order, so the sums are deterministic.
-__global__ __launch_bounds__(256) void chain_moments_kernel(const double *means, const double *covs, int W, int n,
-                                                           double count, const int *wcount, const double *gmean,
-                                                           double *out)
-{   // wcount (may be null): each walker's own sample count (collector windows)
-    __shared__ double red[256];
-    const int nout = gmean ? n * n : 2 + n + 2 * n * n;
-    for (int o = 0; o < nout; o++) {
-        double acc = 0.0;
-        for (int w = threadIdx.x; w < W; w += 256) {
-            const double *m = means + (size_t)w * n;
-            const double *C = covs + (size_t)w * n * n;
-            const double cw = wcount ? (double)wcount[w] : count;
-            double v;
-            if (gmean) {
-                const int i = o / n, j = o % n;
-                v = cw * (m[i] - gmean[i]) * (m[j] - gmean[j]);
-            } else if (o == 0) {
-                v = cw;
-            } else if (o <= n) {
-                v = cw * m[o - 1];
-            } else if (o <= n + n * n) {
-                v = cw * C[o - 1 - n];
-            } else if (o <= n + 2 * n * n) {
-                v = C[o - 1 - n - n * n];
-            } else {
-                v = 1.0;
-            }
-            acc += v;
-        }
-        red[threadIdx.x] = acc;
-        __syncthreads();
-        for (int h = 128; h > 0; h >>= 1) {
-            if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) out[o] = red[0];
-        __syncthreads();
-    }
-}
-
-void chain_moments_launch(const double *means, const double *covs, int W, int n, double count, const int *wcount,
-                          const double *gmean, double *out, hipStream_t stream) {
-    hipLaunchKernelGGL(chain_moments_kernel, dim3(1), dim3(256), 0, stream, means, covs, W, n, count, wcount, gmean,
-                       out);
-    HIP_CHECK(hipGetLastError());
 }
 
 // ------------------------------------------------------------ host side
@@ -3025,7 +1040,7 @@ static bool rot_may_pend(cmbs *s, int fast_only, int g0) {
     return due;
 }
 
-static void rot_schedule_unknown(cmbs *s) { std::fill(s->rot_lp.begin(), s->rot_lp.end(), -1); }
+void rot_schedule_unknown(cmbs *s) { std::fill(s->rot_lp.begin(), s->rot_lp.end(), -1); }
 
 // The in-launch hand-offs' give-up word (the unified launch, the bin co-run):
 // a word of pinned host memory that the kernels write through its device
@@ -3358,11 +1373,7 @@ static StepTail make_tail(cmbs *s, int rd, int wr) {
         // 16-walker body's thread groups (256 / 16) cover the bandpowers
         // (middle launches only: in the accept-only launch that ends a call the
         // chi^2 would sit on the chain's critical path, 21.5 against 23.3 us)
-        t.fold_g = (s->fold_g && wr >= 0 && t.g.d.nX <= MH_THREADS / MB) ? 1 : 0;
-        t.qf_ahead = s->qf_ahead;
-        t.qf_prio = s->qf_prio;
-        t.fold_tpf = s->fold_tpf;
-        t.fold_late_prio = s->fold_late_prio;
+        t.fold_g = (wr >= 0 && t.g.d.nX <= MH_THREADS / MB) ? 1 : 0;
         if (t.fold_g) t.ng = 0;
     }
     if (wr >= 0) {
@@ -3878,200 +1889,6 @@ void sampler_set_groups(cmbs *s, int n_groups) {
     s->n_groups = n_groups;
 }
 
-void sampler_enable_history(cmbs *s, int capacity) {
-    s->hist.alloc((size_t)capacity * (s->n_used + 1) * s->W * 8);   // per step: P(params_used) rows, CurLike row
-    s->hist_cap = capacity;
-    s->hist_count = 0;
-    if (!s->likes.empty()) {   // per step: each likelihood's -lnL at the current point
-        s->hist_terms.alloc((size_t)capacity * s->likes.size() * s->W * 8);
-        HIP_CHECK(hipMemset(s->hist_terms.p, 0, s->hist_terms.bytes));
-    }
-}
-
-void sampler_history_stats(cmbs *s, int first, int last, double *means, double *covs, hipStream_t stream) {
-    if (s->hist_cap == 0) fail(CMBL_ERR_ARG, "history not enabled");
-    if (first < 0 || last < first || last >= s->hist_count || s->hist_count - first > s->hist_cap)
-        fail(CMBL_ERR_ARG, "history rows [%d, %d] not available (count %d, capacity %d)", first, last,
-             s->hist_count, s->hist_cap);
-    const int n = s->n_used;
-    const dim3 gm((s->W + 63) / 64), gc((s->W + 63) / 64, n), blk(64 * HS_PH);
-    const double *h = s->hist.as<double>();
-    auto run = [&](auto kmean, auto kcov) {
-        hipLaunchKernelGGL(kmean, gm, blk, 0, stream, h, s->hist_cap, s->W, n, first, last, means);
-        HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(kcov, gc, blk, 0, stream, h, s->hist_cap, s->W, n, first, last, means, covs);
-        HIP_CHECK(hipGetLastError());
-    };
-    if (n <= 8) run(hist_mean_kernel<8>, hist_cov_kernel<8>);
-    else if (n <= 16) run(hist_mean_kernel<16>, hist_cov_kernel<16>);
-    else if (n <= 32) run(hist_mean_kernel<32>, hist_cov_kernel<32>);
-    else run(hist_mean_kernel<64>, hist_cov_kernel<64>);
-}
-
-void sampler_chain_moments(cmbs *s, int first, int last, const double *gmean, double *out, hipStream_t stream) {
-    const int n = s->n_used;
-    s->mom.grow((size_t)s->W * (n + n * n) * 8);
-    double *means = s->mom.as<double>(), *covs = means + (size_t)s->W * n;
-    sampler_history_stats(s, first, last, means, covs, stream);
-    chain_moments_launch(means, covs, s->W, n, (double)(last - first + 1), nullptr, gmean, out, stream);
-}
-
-void sampler_history_host(cmbs *s, int first, int count, double *out) {
-    if (s->hist_cap == 0) fail(CMBL_ERR_ARG, "history not enabled");
-    const int oldest = std::max(0, s->hist_count - s->hist_cap);
-    if (first < oldest || first + count > s->hist_count)
-        fail(CMBL_ERR_ARG, "history rows [%d, %d) not kept (rows %d..%d)", first, first + count, oldest, s->hist_count - 1);
-    HIP_CHECK(hipDeviceSynchronize());
-    const size_t blk = (size_t)(s->n_used + 1) * s->W;
-    for (int k = 0; k < count; k++) {
-        const int slot = (first + k) % s->hist_cap;
-        HIP_CHECK(hipMemcpy(out + (size_t)k * blk, s->hist.as<double>() + (size_t)slot * blk, blk * 8,
-                            hipMemcpyDeviceToHost));
-    }
-}
-
-void sampler_history_terms_host(cmbs *s, int first, int count, double *out) {
-    if (s->hist_cap == 0) fail(CMBL_ERR_ARG, "history not enabled");
-    const int oldest = std::max(0, s->hist_count - s->hist_cap);
-    if (first < oldest || first + count > s->hist_count)
-        fail(CMBL_ERR_ARG, "history rows [%d, %d) not kept (rows %d..%d)", first, first + count, oldest, s->hist_count - 1);
-    const size_t blk = s->likes.size() * (size_t)s->W;
-    if (blk == 0) return;
-    HIP_CHECK(hipDeviceSynchronize());
-    for (int k = 0; k < count; k++) {
-        const int slot = (first + k) % s->hist_cap;
-        HIP_CHECK(hipMemcpy(out + (size_t)k * blk, s->hist_terms.as<double>() + (size_t)slot * blk, blk * 8,
-                            hipMemcpyDeviceToHost));
-    }
-}
-
-// checkpoint resume of the history ring: rows [first, first + count) as
-// written by sampler_history_host go back to their ring slots, and the ring
-// continues at first + count (the samples the convergence test windows over,
-// TMpiChainCollector_ReadState's Samples%LoadState, SampleCollector.f90:167)
-void sampler_history_restore(cmbs *s, int first, int count, const double *in, const double *terms) {
-    if (s->hist_cap == 0) fail(CMBL_ERR_ARG, "history not enabled");
-    if (first < 0 || count < 0 || count > s->hist_cap)
-        fail(CMBL_ERR_ARG, "history rows [%d, %d) do not fit the ring (capacity %d)", first, first + count,
-             s->hist_cap);
-    HIP_CHECK(hipDeviceSynchronize());
-    const size_t blk = (size_t)(s->n_used + 1) * s->W;
-    for (int k = 0; k < count; k++) {
-        const int slot = (first + k) % s->hist_cap;
-        HIP_CHECK(hipMemcpy(s->hist.as<double>() + (size_t)slot * blk, in + (size_t)k * blk, blk * 8,
-                            hipMemcpyHostToDevice));
-    }
-    const size_t tblk = s->likes.size() * (size_t)s->W;
-    if (terms && tblk)
-        for (int k = 0; k < count; k++) {
-            const int slot = (first + k) % s->hist_cap;
-            HIP_CHECK(hipMemcpy(s->hist_terms.as<double>() + (size_t)slot * tblk, terms + (size_t)k * tblk,
-                                tblk * 8, hipMemcpyHostToDevice));
-        }
-    s->hist_count = first + count;
-}
-
-void sampler_get_state_host(cmbs *s, double *P, double *cur_like, double *mult, int *num_accept) {
-    HIP_CHECK(hipDeviceSynchronize());
-    const int W = s->W, np = s->np;
-    const size_t ld = s->dc.ld;
-    const Rows &R = s->dc.rows;
-    if (P) {
-        std::vector<double> t((size_t)np * ld);
-        HIP_CHECK(hipMemcpy(t.data(), s->dc.sd + (size_t)R.P * ld, t.size() * 8, hipMemcpyDeviceToHost));
-        for (int w = 0; w < W; w++)
-            for (int i = 0; i < np; i++) P[(size_t)w * np + i] = t[(size_t)i * ld + w];
-    }
-    if (cur_like) HIP_CHECK(hipMemcpy(cur_like, s->dc.sd + (size_t)R.L * ld, (size_t)W * 8, hipMemcpyDeviceToHost));
-    if (mult) HIP_CHECK(hipMemcpy(mult, s->dc.sd + (size_t)R.M * ld, (size_t)W * 8, hipMemcpyDeviceToHost));
-    if (num_accept)
-        HIP_CHECK(hipMemcpy(num_accept, s->dc.si + (size_t)R.NACC * ld, (size_t)W * 4, hipMemcpyDeviceToHost));
-}
-
-// Checkpoint image of every walker's chain state: the reference's .chk holds
-// num_sample / MaxLike / num_accept (MCMC.f90:98-114, 199-218) and the
-// proposal matrix (propose.f90:308-325) and restarts from the last chain row
-// with a fresh RNG (GeneralSetup.f90:123-131); this image holds the complete
-// device state instead -- point, CurLike, multiplicity, accept count, RANMAR
-// table and Gaussian1 cache, cyclic-index and rotation state, each
-// likelihood's term at the point -- so a resumed run continues each chain
-// exactly.  Layout: StateHeader, double rows [ND][W], int rows [NI][W],
-// current terms [n_like][W].  The proposal covariance is the caller's part
-// (cmbs_set_covariance before cmbs_load_state).
-struct StateHeader {
-    unsigned magic, version;
-    int W, np, n_used, nblocks, all_n, slow_n, fast_n, R_total, ND, NI, n_like, theory_moved;
-    int coll_cap, pad;      // sample-collector ring (0: not enabled) appended after the terms
-    long long num_drag;
-};
-static constexpr unsigned STATE_MAGIC = 0x53424d43u;   // "CMBS"
-
-size_t sampler_state_bytes(const cmbs *s) {
-    const Rows &R = s->dc.rows;
-    return sizeof(StateHeader) + (size_t)(R.ND + s->likes.size()) * s->W * 8 + (size_t)R.NI * s->W * 4 +
-           sampler_collector_bytes(s);
-}
-
-static StateHeader state_header(const cmbs *s) {
-    const Rows &R = s->dc.rows;
-    return StateHeader{STATE_MAGIC, 2u, s->W, s->np, s->n_used, s->nblocks, s->all_n, s->slow_n, s->fast_n,
-                       s->R_total, R.ND, R.NI, (int)s->likes.size(), s->theory_moved ? 1 : 0,
-                       s->coll.enabled ? s->coll.cap : 0, 0, s->num_drag};
-}
-
-void sampler_save_state(cmbs *s, void *buf, size_t bytes) {
-    if (!s->started) fail(CMBL_ERR_ARG, "no chain state yet: cmbs_set_start first");
-    if (bytes < sampler_state_bytes(s)) fail(CMBL_ERR_ARG, "state buffer too small (%zu < %zu bytes)", bytes,
-                                            sampler_state_bytes(s));
-    HIP_CHECK(hipDeviceSynchronize());
-    const Rows &R = s->dc.rows;
-    const size_t ld = s->dc.ld, W = s->W;
-    char *p = static_cast<char *>(buf);
-    const StateHeader h = state_header(s);
-    std::memcpy(p, &h, sizeof h);
-    p += sizeof h;
-    HIP_CHECK(hipMemcpy2D(p, W * 8, s->dc.sd, ld * 8, W * 8, R.ND, hipMemcpyDeviceToHost));
-    p += (size_t)R.ND * W * 8;
-    HIP_CHECK(hipMemcpy2D(p, W * 4, s->dc.si, ld * 4, W * 4, R.NI, hipMemcpyDeviceToHost));
-    p += (size_t)R.NI * W * 4;
-    if (!s->likes.empty())
-        HIP_CHECK(hipMemcpy2D(p, W * 8, s->dc.cur_terms, ld * 8, W * 8, s->likes.size(), hipMemcpyDeviceToHost));
-    p += s->likes.size() * W * 8;
-    if (s->coll.enabled) sampler_collector_save(s, p);
-}
-
-void sampler_load_state(cmbs *s, const void *buf, size_t bytes) {
-    rot_schedule_unknown(s);
-    if (bytes < sizeof(StateHeader)) fail(CMBL_ERR_ARG, "state image too short");
-    StateHeader h;
-    std::memcpy(&h, buf, sizeof h);
-    if (h.magic != STATE_MAGIC || h.version != 2u) fail(CMBL_ERR_FORMAT, "not a cmbs state image");
-    const StateHeader m = state_header(s);
-    if (h.W != m.W || h.np != m.np || h.n_used != m.n_used || h.nblocks != m.nblocks || h.all_n != m.all_n ||
-        h.slow_n != m.slow_n || h.fast_n != m.fast_n || h.R_total != m.R_total || h.ND != m.ND || h.NI != m.NI ||
-        h.n_like != m.n_like || h.coll_cap != m.coll_cap)
-        fail(CMBL_ERR_ARG,
-             "state image is for a different sampler (W %d np %d blocks %d likelihoods %d; this one W %d np %d "
-             "blocks %d likelihoods %d)", h.W, h.np, h.nblocks, h.n_like, m.W, m.np, m.nblocks, m.n_like);
-    if (bytes < sampler_state_bytes(s)) fail(CMBL_ERR_FORMAT, "state image truncated");
-    const Rows &R = s->dc.rows;
-    const size_t ld = s->dc.ld, W = s->W;
-    const char *p = static_cast<const char *>(buf) + sizeof h;
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemcpy2D(s->dc.sd, ld * 8, p, W * 8, W * 8, R.ND, hipMemcpyHostToDevice));
-    p += (size_t)R.ND * W * 8;
-    HIP_CHECK(hipMemcpy2D(s->dc.si, ld * 4, p, W * 4, W * 4, R.NI, hipMemcpyHostToDevice));
-    p += (size_t)R.NI * W * 4;
-    if (!s->likes.empty())
-        HIP_CHECK(hipMemcpy2D(s->dc.cur_terms, ld * 8, p, W * 8, W * 8, s->likes.size(), hipMemcpyHostToDevice));
-    p += s->likes.size() * W * 8;
-    if (s->coll.enabled) sampler_collector_load(s, p);
-    s->num_drag = h.num_drag;
-    s->theory_moved = h.theory_moved != 0;
-    s->theory_stale = s->theory_moved && !s->likes.empty();
-    s->started = true;
-}
-
 }  // namespace cmamd
 
 #ifdef CMAMD_STAMPS
@@ -4106,6 +1923,15 @@ extern "C" int cmamd_debug_tp_items(const cmbs *s, int *out, int cap) {   // (fi
         for (int q = 0; q < 6; q++) out[6 * k + q] = v[q];
     }
     return s->tpass->n_items();
+}
+extern "C" int cmamd_debug_tail_rows(int nq, int ng, int np, int nm, int *out, int cap) {   // (role, row of the role) per row
+    const std::vector<int2> rows = cmamd::tail_rows(nq, ng, np, nm);
+    const int n = std::min(cap, (int)rows.size());
+    for (int k = 0; k < n; k++) {
+        out[2 * k] = rows[k].x;
+        out[2 * k + 1] = rows[k].y;
+    }
+    return (int)rows.size();
 }
 extern "C" int cmamd_debug_pipeline(cmbs *s, int mode) {   // fast-step schedule (sampler_step): 0 unpipelined,
     if (!s || (mode != 0 && mode != 3)) return -1;   // 3 the unified launch (default), 0 unpipelined

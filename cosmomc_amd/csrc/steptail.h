@@ -36,10 +36,6 @@ struct StepTail {
     SmallGaussLaunch g{};
     int ng = 0;              // chi^2 workgroups, 0: none
     int fold_g = 0;          // the chi^2 runs inside the Metropolis workgroups (16 walkers each), not as rows
-    int qf_ahead = 0;        // middle launches: the quadratic form's two-step-ahead form (qfs_body_nj)
-    int fold_late_prio = 0;  // the Metropolis workgroups take issue priority only after the folded chi^2
-    int qf_prio = 0;         // the quadratic-form waves at issue priority 2
-    int fold_tpf = 1;        // the folded chi^2's tasks in flight per thread group
     TPDev tp{};              // the raw pass (tp.out[*].out: the raw-sum buffers it writes)
     const double *dl = nullptr;
     long long ld_field = 0, ld_walker = 0;
@@ -50,7 +46,7 @@ struct StepTail {
 // Workgroup roles by rows of 8 (block b runs on XCD b % 8, so each role's own
 // block numbering keeps the XCD placement its body assumes: qf_place,
 // TheoryPass::plan_units): row k is role rows[k].x's rows[k].y-th row.  The nm
-// Metropolis workgroups come last.
+// Metropolis workgroups come last beside chi^2 rows (ng > 0), else first.
 enum { TAIL_QF = 0, TAIL_GAUSS = 1, TAIL_PASS = 2, TAIL_MH = 3 };
 std::vector<int2> tail_rows(int nq, int ng, int np, int nm);
 
@@ -60,6 +56,5 @@ struct StepTailPlan {
     int key[3] = {-1, -1, -1};
     int nrows = 0;
 };
-
 
 }  // namespace cmamd

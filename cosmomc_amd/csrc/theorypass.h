@@ -14,9 +14,6 @@ namespace cmamd {
 static constexpr int TP_MAXOUT = 2;    // likelihoods per pass
 static constexpr int TP_CHUNK = 64;    // l per weight chunk
 static constexpr int TP_MAXCOL = 64;   // columns per work item (four 16-column MFMA blocks)
-#ifndef CMAMD_TP_MAXL
-#define CMAMD_TP_MAXL 352
-#endif
 // l per work item, unless overlapping columns force more (at most
 // TP_MAXSTEP * 32 - 1 in any case).  Round 2 (the standalone pass alone):
 // 288 (9 steps), 22.7 us against 24.0 (256), 23.2 (272), 23.3 (300), 23.6 (320),
@@ -25,10 +22,10 @@ static constexpr int TP_MAXCOL = 64;   // columns per work item (four 16-column 
 // 352 (11 steps), middle launch 33.2-33.7 -> 32.0-32.5 us and the drag step
 // 407-413 -> 399-405 us, against 192 / 224 / 256 / 320 / 336 / 368 / 384 / 416 /
 // 448 (34.2 / 34.6 / 33.2 / 33.2 / 32.6-32.9 / 32.9-33.0 / 32.6-32.7 / 33.3 / 34.0 us
-// a launch; tools/gpu_r6j.sh; the drag's pair pass 165-180 us a drag step at
+// a launch; DESIGN.md section 5's table; the drag's pair pass 165-180 us a drag step at
 // 320-368 against 152-153 at 352); at 480
 // some l range needs more than TP_MAXCOL columns and the fused pass is not built
-static constexpr int TP_MAXL = CMAMD_TP_MAXL;
+static constexpr int TP_MAXL = 352;
 
 struct TPOut {            // a stage's output for one launch
     int kind;             // WinStage::kind

@@ -114,3 +114,36 @@ def test_plik_dataset_written_is_readable_by_host_ini(tmp_path):
     ini = IniFile(path)
     assert ini["use_cl"] == "TT TE EE"
     assert os.path.exists(ini.relative_filename("cov_file"))
+
+
+QF, GAUSS, PASS, MH = 0, 1, 2, 3   # steptail.h's roles
+
+
+def tail_rows(nq, ng, np_, nm):
+    out = np.full(2 * 512, -1, dtype=np.int32)
+    n = N.lib().cmamd_debug_tail_rows(nq, ng, np_, nm, out.ctypes.data_as(C.c_void_p), 512)
+    assert 0 <= n <= 512
+    return [tuple(r) for r in out[:2 * n].reshape(n, 2)]
+
+
+def role_rows(role, n):
+    return [(role, k) for k in range(n)]
+
+
+def test_unified_launch_row_order():
+    """The unified step launch's rows of 8 workgroups (steptail.hip tail_rows),
+    as (role, the role's own row index from 0): with chi^2 rows the tails come
+    first and the Metropolis rows last; with the chi^2 folded into the
+    Metropolis workgroups those come first."""
+    # the headline's middle launch: 64 Metropolis workgroups, 480 quadratic-form, 512 pass
+    assert tail_rows(480, 0, 512, 64) == role_rows(MH, 8) + role_rows(QF, 60) + role_rows(PASS, 64)
+    # its accept-only launch: 256 chi^2 workgroups as rows, no pass
+    assert tail_rows(480, 256, 0, 64) == role_rows(GAUSS, 32) + role_rows(QF, 60) + role_rows(MH, 8)
+    # a call's first launch: the proposal and the pass only (no chi^2 rows, so the Metropolis rows lead)
+    assert tail_rows(0, 0, 512, 64) == role_rows(MH, 8) + role_rows(PASS, 64)
+    # ragged counts round up to whole rows
+    assert tail_rows(9, 1, 1, 1) == role_rows(GAUSS, 1) + role_rows(QF, 2) + role_rows(PASS, 1) + role_rows(MH, 1)
+    # a short buffer gets the first rows and the whole count
+    out = np.full(4, -1, dtype=np.int32)
+    assert N.lib().cmamd_debug_tail_rows(480, 0, 512, 64, out.ctypes.data_as(C.c_void_p), 2) == 132
+    assert out.tolist() == [MH, 0, MH, 1]

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Interleaved A/B of the headline bench under environment switches.
-#   tools/gpu_ab_env.sh "base" "CMAMD_PIPE=0" "CMAMD_UNI_WT=8" ...
+#   tools/gpu_ab_env.sh "base" "CMAMD_PIPE=0" "COSMOMC_AMD_LIB=/path/to/another/libcosmomc_amd.so" ...
 # Each argument is one variant ("base": no extra environment); REPS (default 2)
 # rounds run every variant in turn; BENCH_ARGS replaces the default bench
 # arguments (headline only, 300 steps).

@@ -39,7 +39,7 @@ if __name__ == "__main__":
         s = st[st[:, 4] > 0].astype(np.int64)
         t0 = s[:, 0].min()
         us = lambda x: (x - t0) / 100.0
-        print(f"{which} ({os.environ.get('CMAMD_TAIL_ORDER', 'default order')}): quantiles 0/10/50/90/100, "
+        print(f"{which}: quantiles 0/10/50/90/100, "
               f"us from the first block's start; launch {us(s[:, 3].max()):.2f} us")
         for r, name in ROLES.items():
             b = s[s[:, 4] == r]
