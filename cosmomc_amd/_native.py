@@ -43,6 +43,15 @@ class CmbsConfig(C.Structure):
                 ("lincomb_std", C.POINTER(C.c_double))]
 
 
+class CmbtConfig(C.Structure):
+    _fields_ = [("n_in", C.c_int), ("param_index", C.POINTER(C.c_int)),
+                ("center", C.POINTER(C.c_double)), ("scale", C.POINTER(C.c_double)),
+                ("lo", C.POINTER(C.c_double)), ("hi", C.POINTER(C.c_double)),
+                ("n_terms", C.c_int), ("exponents", C.POINTER(C.c_int)),
+                ("n_fields", C.c_int), ("fields", C.POINTER(C.c_int)), ("lmax", C.c_int),
+                ("coef", C.POINTER(C.c_double))]
+
+
 _lib = None
 
 # cmbs_theory_fn: int (*)(void *user, int W, const double *P_end, long long ld, void *stream)
@@ -107,6 +116,12 @@ def lib():
         L.cmbs_step_drag.argtypes = [vp, i, d, THEORY_FN, vp, vp]
         L.cmbs_step_theory.argtypes = [vp, i, THEORY_FN, vp, vp]
         L.cmbs_refresh_theory.argtypes = [vp, THEORY_FN, vp, vp]
+        L.cmbt_create.argtypes = [C.POINTER(CmbtConfig), C.POINTER(vp), C.c_char_p, sz]
+        L.cmbt_destroy.argtypes = [vp]
+        L.cmbt_last_error.argtypes = [vp]
+        L.cmbt_last_error.restype = C.c_char_p
+        L.cmbt_eval.argtypes = [vp, i, vp, ll, i, vp, ll, ll, vp, vp]
+        L.cmbs_set_theory_calculator.argtypes = [vp, vp]
         L.cmbs_collector_enable.argtypes = [vp, i]
         L.cmbs_collector_add.argtypes = [vp, vp, i, i, i, vp]
         L.cmbs_collector_state_host.argtypes = [vp, vp, vp, vp, vp]
@@ -144,7 +159,7 @@ def check(rc: int, handle=None, kind: str = "cmbl"):
     if rc != 0:
         msg = ""
         if handle is not None:
-            fn = lib().cmbl_last_error if kind == "cmbl" else lib().cmbs_last_error
+            fn = {"cmbl": lib().cmbl_last_error, "cmbs": lib().cmbs_last_error, "cmbt": lib().cmbt_last_error}[kind]
             msg = (fn(handle) or b"").decode()
         raise NativeError(rc, msg)
 

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "sampler.h"
+#include "theorycalc.h"
 
 namespace cmamd {
 void sampler_create(cmbs *s, const cmbs_config_t *cfg);
@@ -372,6 +373,39 @@ int cmbs_refresh_theory(cmbs_t *s, cmbs_theory_fn theory_fn, void *user, void *s
     if (!s) return CMBL_ERR_ARG;
     return guarded(&s->last_error,
                    [&] { cmamd::sampler_refresh_theory(s, theory_fn, user, (hipStream_t)stream); });
+}
+
+int cmbt_create(const cmbt_config_t *cfg, cmbt_t **out, char *errbuf, size_t errlen) {
+    std::string err;
+    if (!cfg || !out) {
+        put_err(errbuf, errlen, "cmbt_create: null argument");
+        return CMBL_ERR_ARG;
+    }
+    *out = nullptr;
+    std::unique_ptr<cmbt> t(new cmbt);
+    int rc = guarded(&err, [&] { cmamd::theorycalc_create(t.get(), cfg); });
+    if (rc) {
+        put_err(errbuf, errlen, err.c_str());
+        return rc;
+    }
+    *out = t.release();
+    return CMBL_OK;
+}
+
+void cmbt_destroy(cmbt_t *t) { delete t; }
+const char *cmbt_last_error(const cmbt_t *t) { return t ? t->last_error.c_str() : ""; }
+
+int cmbt_eval(cmbt_t *t, int W, const double *P, long long ld, int num_params, double *dl, long long ld_field,
+              long long ld_walker, int *fail, void *stream) {
+    if (!t) return CMBL_ERR_ARG;
+    return guarded(&t->last_error, [&] {
+        cmamd::theorycalc_eval(t, W, P, ld, num_params, dl, ld_field, ld_walker, fail, (hipStream_t)stream);
+    });
+}
+
+int cmbs_set_theory_calculator(cmbs_t *s, cmbt_t *calc) {
+    if (!s) return CMBL_ERR_ARG;
+    return guarded(&s->last_error, [&] { cmamd::sampler_set_theory_calculator(s, calc); });
 }
 
 int cmbs_collector_enable(cmbs_t *s, int sample_capacity) {

@@ -195,6 +195,11 @@ struct cmbs {
     struct EndTheory { double *dl = nullptr; long long ld_field = 0, ld_walker = 0; };
     EndTheory end_theory[cmamd::MAXLIKE];
     long long num_drag = 0;
+    // theory calculator (cmbs_set_theory_calculator; not owned): with no theory
+    // function, the trial theories come from it, and calc_fail [ld] holds the
+    // walkers whose trial lies outside its box
+    cmbt *calc = nullptr;
+    cmamd::DevBuf calc_fail;
     // the sampler swapped accepted trial theories into the walkers' theory rows
     // (cmbs_step_theory / cmbs_step_drag); after a resume those rows must be
     // recomputed at the restored points (cmbs_refresh_theory) before stepping
@@ -281,6 +286,7 @@ void sampler_set_trial_theory(cmbs *s, int like_index, double *dl_end, long long
 void sampler_step_drag(cmbs *s, int n_steps, double dragging_steps, cmbs_theory_fn fn, void *user, hipStream_t stream);
 void sampler_step_theory(cmbs *s, int n_steps, cmbs_theory_fn fn, void *user, hipStream_t stream);
 void sampler_refresh_theory(cmbs *s, cmbs_theory_fn fn, void *user, hipStream_t stream);
+void sampler_set_theory_calculator(cmbs *s, cmbt *calc);
 void sampler_collector_enable(cmbs *s, int samp_capacity);
 void sampler_collector_add(cmbs *s, const int *steps, int nsteps, int min_update, int check_burn, hipStream_t st);
 void sampler_collector_state_host(cmbs *s, int *start, int *count, int *burn, int *thin);

@@ -36,6 +36,7 @@
 #include "quadform.h"
 #include "sampler.h"
 #include "smallgauss.h"
+#include "theorycalc.h"
 #ifdef CMAMD_STAMPS
 namespace cmamd {
 // mh_step_kernel (tools/uni_stamps.py), [0] the middle launches, [1] the last
@@ -1705,6 +1706,46 @@ static bool same_theory_swap(const cmbs *s, int i) {
     return false;
 }
 
+// ---- theory calculator (cmbs_set_theory_calculator): the trial theories
+// without a theory function
+void sampler_set_theory_calculator(cmbs *s, cmbt *calc) {
+    s->calc = calc;
+    if (calc && !s->calc_fail.p) s->calc_fail.alloc((size_t)s->dc.ld * 4);
+}
+
+// the calculator at parameter rows Prows [np][ld] into every distinct
+// trial-theory buffer (one launch each), the walkers outside its box flagged
+// in calc_fail
+static void calc_trial_theory(cmbs *s, const double *Prows, hipStream_t stream) {
+    for (size_t i = 0; i < s->likes.size(); i++) {
+        const auto &e = s->end_theory[i];
+        bool seen = false;
+        for (size_t j = 0; j < i && !seen; j++) {
+            const auto &ej = s->end_theory[j];
+            seen = ej.dl == e.dl && ej.ld_field == e.ld_field && ej.ld_walker == e.ld_walker;
+        }
+        if (seen) continue;
+        theorycalc_eval(s->calc, s->W, Prows, (long long)s->dc.ld, s->np, e.dl, e.ld_field, e.ld_walker,
+                        s->calc_fail.as<int>(), stream);
+    }
+}
+
+// A trial outside the calculator's box: every likelihood term becomes logZero,
+// so target_like gives logZero as for a trial outside the sampler's bounds
+// (the calculator's error flag, calclike.f90:308-313)
+__global__ void calc_fail_terms(const int *__restrict__ flag, double *terms, int n_like, int W, size_t ld)
+{
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= W || flag[w] == 0) return;
+    for (int l = 0; l < n_like; l++) terms[(size_t)l * ld + w] = LOGZERO;
+}
+
+static void apply_calc_fail(cmbs *s, hipStream_t stream) {
+    hipLaunchKernelGGL(calc_fail_terms, dim3((s->W + 255) / 256), dim3(256), 0, stream, s->calc_fail.as<int>(),
+                       s->like_terms.as<double>(), (int)s->likes.size(), s->W, (size_t)s->dc.ld);
+    HIP_CHECK(hipGetLastError());
+}
+
 void sampler_step_drag(cmbs *s, int n_steps, double dragging_steps, cmbs_theory_fn fn, void *user,
                        hipStream_t stream) {
     rot_schedule_unknown(s);           // the drag proposals move the blocks' loop indices
@@ -1718,7 +1759,7 @@ void sampler_step_drag(cmbs *s, int n_steps, double dragging_steps, cmbs_theory_
     const int nl = (int)s->likes.size();
     for (int i = 0; i < nl; i++)
         if (!s->end_theory[i].dl) fail(CMBL_ERR_ARG, "dragging needs an end-point theory buffer for likelihood %d", i);
-    if (nl > 0 && !fn) fail(CMBL_ERR_ARG, "dragging with data likelihoods needs a theory function");
+    if (nl > 0 && !fn && !s->calc) fail(CMBL_ERR_ARG, "dragging with data likelihoods needs a theory function");
     const size_t ld = s->dc.ld;
     const int np = s->np;
     if (!s->drag_dd.p) {
@@ -1757,8 +1798,10 @@ void sampler_step_drag(cmbs *s, int n_steps, double dragging_steps, cmbs_theory_
         launch_drag<0>(s, g, HistRow{}, stream);
         if (nl > 0) {
             const double *Pend = s->dc.sd + (size_t)s->dc.rows.T * ld;
-            if (fn(user, s->W, Pend, (long long)ld, stream) != 0) fail(CMBL_ERR_ARG, "theory function failed");
+            if (!fn) calc_trial_theory(s, Pend, stream);
+            else if (fn(user, s->W, Pend, (long long)ld, stream) != 0) fail(CMBL_ERR_ARG, "theory function failed");
             if (!eval_likes_drag_pair(s, stream, false)) eval_likes_drag(s, 1, stream);
+            if (!fn) apply_calc_fail(s, stream);   // a flagged end point aborts its drag in stage 1
         }
         launch_drag<1>(s, g, HistRow{}, stream);
         for (int is = 1; is <= interp - 1; is++) {
@@ -1812,15 +1855,18 @@ void sampler_step_theory(cmbs *s, int n_steps, cmbs_theory_fn fn, void *user, hi
         sampler_step(s, n_steps, 0, stream);
         return;
     }
-    if (!fn) fail(CMBL_ERR_ARG, "cmbs_step_theory needs a theory function");
+    if (!fn && !s->calc) fail(CMBL_ERR_ARG, "cmbs_step_theory needs a theory function");
     for (size_t i = 0; i < s->likes.size(); i++) {
         if (!s->end_theory[i].dl) fail(CMBL_ERR_ARG, "likelihood %zu has no trial-theory buffer", i);
         if (s->likes[i].ld_walker == 0) fail(CMBL_ERR_ARG, "slow steps need per-walker theory rows");
     }
     const double *Ptrial = s->dc.sd + (size_t)s->dc.rows.T * s->dc.ld;
     auto trial_likes = [&]() {
-        if (fn(user, s->W, Ptrial, (long long)s->dc.ld, stream) != 0) fail(CMBL_ERR_ARG, "theory function failed");
+        if (!fn) calc_trial_theory(s, Ptrial, stream);
+        else if (fn(user, s->W, Ptrial, (long long)s->dc.ld, stream) != 0)
+            fail(CMBL_ERR_ARG, "theory function failed");
         eval_likes_drag(s, 1, stream);
+        if (!fn) apply_calc_fail(s, stream);
     };
     launch_mh(s, false, true, 0, HistRow{}, stream, 0, s->W);
     trial_likes();
@@ -1850,13 +1896,24 @@ __global__ void copy_theory_rows(int W, const double *src, long long src_ld, dou
 
 void sampler_refresh_theory(cmbs *s, cmbs_theory_fn fn, void *user, hipStream_t stream) {
     if (!s->started) fail(CMBL_ERR_ARG, "no chain state: cmbs_set_start or cmbs_load_state first");
-    if (!fn) fail(CMBL_ERR_ARG, "cmbs_refresh_theory needs a theory function");
+    if (!fn && !s->calc) fail(CMBL_ERR_ARG, "cmbs_refresh_theory needs a theory function");
     for (size_t i = 0; i < s->likes.size(); i++) {
         if (!s->end_theory[i].dl) fail(CMBL_ERR_ARG, "likelihood %zu has no trial-theory buffer", i);
         if (s->likes[i].ld_walker == 0) fail(CMBL_ERR_ARG, "per-walker theory rows needed (ld_walker > 0)");
     }
     const double *Pcur = s->dc.sd + (size_t)s->dc.rows.P * s->dc.ld;
-    if (fn(user, s->W, Pcur, (long long)s->dc.ld, stream) != 0) fail(CMBL_ERR_ARG, "theory function failed");
+    if (!fn) {   // the calculator: a point outside its box has no theory to resume with
+        calc_trial_theory(s, Pcur, stream);
+        std::vector<int> bad(s->likes.empty() ? 0 : s->W);
+        HIP_CHECK(hipMemcpyAsync(bad.data(), s->calc_fail.p, bad.size() * 4, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        const long n_bad = (long)std::count_if(bad.begin(), bad.end(), [](int b) { return b != 0; });
+        if (n_bad > 0)
+            fail(CMBL_ERR_NUMERIC, "cmbs_refresh_theory: %ld of %d walkers lie outside the theory calculator's box",
+                 n_bad, s->W);
+    } else if (fn(user, s->W, Pcur, (long long)s->dc.ld, stream) != 0) {
+        fail(CMBL_ERR_ARG, "theory function failed");
+    }
     for (size_t i = 0; i < s->likes.size(); i++) {
         const auto &e = s->end_theory[i];
         const auto &l = s->likes[i];

@@ -1,0 +1,35 @@
+// Polynomial theory calculator (cmbt_*): a response surface of D_l in the slow
+// parameters, evaluated on the device straight into a theory buffer.  It takes
+// the place of the reference's calculator object in its emulator form
+// (Calculator_PICO.f90: a polynomial fit of the C_l; a point outside the
+// training box gives error = 1, which TheoryLike_GetLogLikeMain turns into
+// logZero, calclike.f90:308-313).
+#pragma once
+
+#include <string>
+#include <vector>
+
+#include "common.h"
+
+namespace cmamd {
+// theory_calc_kernel's tile: TC_TW walkers x TC_TN consecutive l of one field
+// per workgroup, the coefficient table staged through LDS TC_KC terms at a time
+constexpr int TC_TW = 32, TC_TN = 256, TC_KC = 8, TC_THREADS = 256;
+constexpr int TC_MAXIN = 16, TC_MAXTERMS = 256, TC_MAXORDER = 4;
+}  // namespace cmamd
+
+struct cmbt {
+    int n_in = 0, K = 0, Kp = 0, n_fields = 0, lmax = 0, Lp = 0;
+    std::vector<int> pidx;        // 1-based indices into P
+    std::string last_error;
+    // device tables: meta [4][TC_MAXIN] (lo, hi, center, scale), pidx [n_in],
+    // fields [n_fields], expo [Kp] (4 bits per input), coef [n_fields][Kp][Lp]
+    // (terms padded to TC_KC and l to TC_TN with zeros)
+    cmamd::DevBuf meta, pidx_d, fields_d, expo, coef;
+};
+
+namespace cmamd {
+void theorycalc_create(cmbt *t, const cmbt_config_t *cfg);
+void theorycalc_eval(cmbt *t, int W, const double *P, long long ld, int num_params, double *dl, long long ld_field,
+                     long long ld_walker, int *fail_flags, hipStream_t stream);
+}  // namespace cmamd

@@ -1,0 +1,260 @@
+// Polynomial theory calculator: dl[w][field][l] = sum_k basis_k(w) coef[k][field][l],
+// a GEMM out[W x N] = B[W x K] . C[K x N] whose left operand (the monomials of
+// every walker's scaled slow parameters) is built in the launch from the
+// sampler's parameter rows and whose right operand (the coefficient table)
+// stays on the device.  One launch fills one theory buffer.
+//
+// Arithmetic: explicit f64 fma in ascending k from +0.0 (the build has
+// -ffp-contract=off, so the fusion is written out).  On gfx950 the vector and
+// the matrix f64 peak rates are the same, so the register-tiled fma gives up
+// no throughput against v_mfma_f64_16x16x4f64 and keeps the summation order
+// plain: a walker's bits depend on neither W, its place in the batch nor the
+// strides, and the zero padding of k adds exact zeros.
+#include <cstdint>
+
+#include "theorycalc.h"
+
+namespace cmamd {
+
+struct TheoryCalcArgs {
+    const double *meta;                  // [4][TC_MAXIN]: lo, hi, center, scale
+    const int *pidx, *fields;
+    const unsigned long long *expo;      // [Kp] 4 bits per input, input 0 lowest
+    const double *coef;                  // [n_fields][Kp][Lp]
+    int n_in, K, Kp, lmax, Lp, ntl, W;
+    const double *P;
+    long long ld;
+    double *dl;
+    long long ld_field, ld_walker;
+    int *fail;
+};
+
+// Workgroup (x: field j and l tile, y: walker tile): TC_TW walkers x TC_TN l.
+// Thread t holds 8 walkers (its wave's) x 4 l (2 * lane, + 1 and the same 128
+// further on), so a wave stores two 1 KB runs of consecutive l per walker row.
+__global__ __launch_bounds__(TC_THREADS) void theory_calc_kernel(TheoryCalcArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    double *Bs = lds;                              // [Kp][TC_TW] monomials
+    double *Cs = Bs + (size_t)a.Kp * TC_TW;        // [TC_KC][TC_TN] coefficient chunk
+    double *xs = Cs;                               // before the first chunk: [n_in][TC_TW] scaled inputs
+    const int t = threadIdx.x;
+    const int w0 = blockIdx.y * TC_TW;
+    const int j = blockIdx.x / a.ntl, l0 = (blockIdx.x % a.ntl) * TC_TN;
+
+    // validity box on the raw parameters (equality passes, NaN fails); a failed
+    // walker is evaluated at its inputs clamped into the box (NaN: the centre),
+    // so the buffer never holds junk
+    if (t < TC_TW) {
+        const int w = w0 + t;
+        int bad = 0;
+        for (int i = 0; i < a.n_in; i++) {
+            double x = 0.0;
+            if (w < a.W) {
+                double p = a.P[(size_t)(a.pidx[i] - 1) * a.ld + w];
+                const double lo = a.meta[i], hi = a.meta[TC_MAXIN + i];
+                const double c = a.meta[2 * TC_MAXIN + i], s = a.meta[3 * TC_MAXIN + i];
+                if (!(p >= lo && p <= hi)) {
+                    bad = 1;
+                    if (p != p) p = c;
+                    p = p < lo ? lo : (p > hi ? hi : p);
+                }
+                x = (p - c) / s;
+            }
+            xs[i * TC_TW + t] = x;
+        }
+        if (a.fail && blockIdx.x == 0 && w < a.W) a.fail[w] = bad;
+    }
+    __syncthreads();
+    // basis_k = prod_i x_i^e_ki from 1.0, inputs ascending, powers by repeated multiplication
+    for (int idx = t; idx < a.Kp * TC_TW; idx += TC_THREADS) {
+        const int k = idx / TC_TW, wl = idx % TC_TW;
+        double b = 0.0;                            // the padding of k: exact zeros
+        if (k < a.K) {
+            unsigned long long e = a.expo[k];
+            b = 1.0;
+            for (int i = 0; i < a.n_in; i++, e >>= 4) {
+                const double x = xs[i * TC_TW + wl];
+                for (int r = (int)(e & 15); r > 0; r--) b *= x;
+            }
+        }
+        Bs[idx] = b;
+    }
+
+    const int lane = t & 63, wv = t >> 6;
+    double acc[8][4];
+#pragma unroll
+    for (int r = 0; r < 8; r++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) acc[r][q] = 0.0;
+    // chunk loads: TC_KC rows x TC_TN doubles = 4 double2 a thread, the next
+    // chunk fetched into registers while this one is multiplied
+    const double *Cg = a.coef + (size_t)j * a.Kp * a.Lp + l0;
+    constexpr int C2 = TC_TN / 2;                  // double2 per chunk row
+    constexpr int NPRE = TC_KC * C2 / TC_THREADS;
+    static_assert(NPRE == 4, "four double2 of the chunk a thread");
+    // this thread's pieces of chunk row r = q * (TC_THREADS / C2) + t / C2
+    const double *Ct = Cg + (size_t)(t / C2) * a.Lp + 2 * (t % C2);
+    const size_t rstep = (size_t)(TC_THREADS / C2) * a.Lp;
+#define TC_FETCH(k0)                                                                  \
+    p0 = *reinterpret_cast<const double2 *>(Ct + (size_t)(k0) * a.Lp);                \
+    p1 = *reinterpret_cast<const double2 *>(Ct + (size_t)(k0) * a.Lp + rstep);        \
+    p2 = *reinterpret_cast<const double2 *>(Ct + (size_t)(k0) * a.Lp + 2 * rstep);    \
+    p3 = *reinterpret_cast<const double2 *>(Ct + (size_t)(k0) * a.Lp + 3 * rstep);
+    double2 p0, p1, p2, p3;
+    TC_FETCH(0)
+    double2 *Cs2 = reinterpret_cast<double2 *>(Cs);
+    for (int k0 = 0; k0 < a.Kp; k0 += TC_KC) {
+        __syncthreads();                           // xs / the previous chunk have been read
+        Cs2[t] = p0;
+        Cs2[t + TC_THREADS] = p1;
+        Cs2[t + 2 * TC_THREADS] = p2;
+        Cs2[t + 3 * TC_THREADS] = p3;
+        __syncthreads();
+        if (k0 + TC_KC < a.Kp) {
+            TC_FETCH(k0 + TC_KC)
+        }
+#pragma unroll
+        for (int kk = 0; kk < TC_KC; kk++) {
+            const double2 c01 = Cs2[kk * C2 + lane], c23 = Cs2[kk * C2 + 64 + lane];   // 16-byte lane stride: no bank conflict
+            const double2 *bp = reinterpret_cast<const double2 *>(Bs + (size_t)(k0 + kk) * TC_TW + wv * 8);
+            const double2 b01 = bp[0], b23 = bp[1], b45 = bp[2], b67 = bp[3];
+#define TC_ROW(r, bb)                                   \
+    acc[r][0] = __builtin_fma(bb, c01.x, acc[r][0]);    \
+    acc[r][1] = __builtin_fma(bb, c01.y, acc[r][1]);    \
+    acc[r][2] = __builtin_fma(bb, c23.x, acc[r][2]);    \
+    acc[r][3] = __builtin_fma(bb, c23.y, acc[r][3]);
+            TC_ROW(0, b01.x) TC_ROW(1, b01.y) TC_ROW(2, b23.x) TC_ROW(3, b23.y)
+            TC_ROW(4, b45.x) TC_ROW(5, b45.y) TC_ROW(6, b67.x) TC_ROW(7, b67.y)
+#undef TC_ROW
+        }
+    }
+#undef TC_FETCH
+    // stores: per walker row two wave-wide runs of consecutive l (1 KB each),
+    // 16 bytes a lane; a row that is only 8-byte aligned (odd ld_field or
+    // ld_walker) and the row's tail take 8-byte stores
+    double *colp = a.dl + (long long)a.fields[j] * a.ld_field;
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        const int w = w0 + wv * 8 + r;
+        if (w < a.W) {
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int l = l0 + h * (TC_TN / 2) + 2 * lane;
+                double *p = colp + (long long)w * a.ld_walker + l;
+                const double v0 = acc[r][2 * h], v1 = acc[r][2 * h + 1];
+                if (l + 1 <= a.lmax && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+                    *reinterpret_cast<double2 *>(p) = make_double2(v0, v1);
+                } else {
+                    if (l <= a.lmax) p[0] = v0;
+                    if (l + 1 <= a.lmax) p[1] = v1;
+                }
+            }
+        }
+    }
+}
+
+static size_t tc_lds_bytes(int Kp) { return ((size_t)Kp * TC_TW + (size_t)TC_KC * TC_TN) * 8; }
+
+void theorycalc_create(cmbt *t, const cmbt_config_t *c) {
+    if (c->n_in < 1 || c->n_in > TC_MAXIN) fail(CMBL_ERR_ARG, "cmbt_create: n_in must be in 1..%d", TC_MAXIN);
+    if (c->n_terms < 1 || c->n_terms > TC_MAXTERMS)
+        fail(CMBL_ERR_ARG, "cmbt_create: n_terms must be in 1..%d", TC_MAXTERMS);
+    if (c->n_fields < 1 || c->n_fields > CMBL_NFIELDS)
+        fail(CMBL_ERR_ARG, "cmbt_create: n_fields must be in 1..%d", CMBL_NFIELDS);
+    if (c->lmax < 0) fail(CMBL_ERR_ARG, "cmbt_create: lmax must not be negative");
+    if (!c->param_index || !c->center || !c->scale || !c->lo || !c->hi || !c->exponents || !c->fields || !c->coef)
+        fail(CMBL_ERR_ARG, "cmbt_create: null table");
+    const int n_in = c->n_in, K = c->n_terms, nf = c->n_fields;
+    std::vector<double> meta(4 * TC_MAXIN, 0.0);
+    for (int i = 0; i < n_in; i++) {
+        if (c->param_index[i] < 1) fail(CMBL_ERR_ARG, "cmbt_create: param_index %d is not 1-based", c->param_index[i]);
+        if (!(c->scale[i] != 0.0)) fail(CMBL_ERR_ARG, "cmbt_create: scale of input %d must not be 0", i);
+        if (!(c->lo[i] <= c->hi[i])) fail(CMBL_ERR_ARG, "cmbt_create: input %d has lo > hi", i);
+        meta[i] = c->lo[i];
+        meta[TC_MAXIN + i] = c->hi[i];
+        meta[2 * TC_MAXIN + i] = c->center[i];
+        meta[3 * TC_MAXIN + i] = c->scale[i];
+    }
+    const int Kp = (K + TC_KC - 1) / TC_KC * TC_KC;
+    std::vector<unsigned long long> expo(Kp, 0ull);
+    for (int k = 0; k < K; k++) {
+        int sum = 0;
+        for (int i = 0; i < n_in; i++) {
+            const int e = c->exponents[(size_t)k * n_in + i];
+            if (e < 0) fail(CMBL_ERR_ARG, "cmbt_create: negative exponent in term %d", k);
+            sum += e;
+            if (sum > TC_MAXORDER) fail(CMBL_ERR_ARG, "cmbt_create: term %d has order above %d", k, TC_MAXORDER);
+            expo[k] |= (unsigned long long)e << (4 * i);
+        }
+    }
+    bool seen[CMBL_NFIELDS] = {};
+    for (int j = 0; j < nf; j++) {
+        const int f = c->fields[j];
+        if (f < 0 || f >= CMBL_NFIELDS) fail(CMBL_ERR_ARG, "cmbt_create: field %d outside 0..%d", f, CMBL_NFIELDS - 1);
+        if (seen[f]) fail(CMBL_ERR_ARG, "cmbt_create: field %d repeated", f);
+        seen[f] = true;
+    }
+    const int L = c->lmax + 1, Lp = (L + TC_TN - 1) / TC_TN * TC_TN;
+    std::vector<double> coef((size_t)nf * Kp * Lp, 0.0);
+    for (int k = 0; k < K; k++)
+        for (int j = 0; j < nf; j++)
+            std::copy(c->coef + ((size_t)k * nf + j) * L, c->coef + ((size_t)k * nf + j + 1) * L,
+                      coef.begin() + ((size_t)j * Kp + k) * Lp);
+    t->n_in = n_in;
+    t->K = K;
+    t->Kp = Kp;
+    t->n_fields = nf;
+    t->lmax = c->lmax;
+    t->Lp = Lp;
+    t->pidx.assign(c->param_index, c->param_index + n_in);
+    t->meta.alloc(meta.size() * 8);
+    t->meta.upload(meta.data(), meta.size() * 8);
+    t->pidx_d.alloc((size_t)n_in * 4);
+    t->pidx_d.upload(t->pidx.data(), (size_t)n_in * 4);
+    t->fields_d.alloc((size_t)nf * 4);
+    t->fields_d.upload(c->fields, (size_t)nf * 4);
+    t->expo.alloc((size_t)Kp * 8);
+    t->expo.upload(expo.data(), (size_t)Kp * 8);
+    t->coef.alloc(coef.size() * 8);
+    t->coef.upload(coef.data(), coef.size() * 8);
+    HIP_CHECK(hipFuncSetAttribute((const void *)theory_calc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)tc_lds_bytes(TC_MAXTERMS)));
+}
+
+void theorycalc_eval(cmbt *t, int W, const double *P, long long ld, int num_params, double *dl, long long ld_field,
+                     long long ld_walker, int *fail_flags, hipStream_t stream) {
+    if (W <= 0) fail(CMBL_ERR_ARG, "cmbt_eval: W must be positive");
+    if (!P || !dl) fail(CMBL_ERR_ARG, "cmbt_eval: null buffer");
+    if (ld < W) fail(CMBL_ERR_ARG, "cmbt_eval: ld %lld below W %d", ld, W);
+    for (int p : t->pidx)
+        if (p > num_params) fail(CMBL_ERR_ARG, "cmbt_eval: param_index %d outside 1..%d", p, num_params);
+    if (ld_walker == 0) fail(CMBL_ERR_ARG, "cmbt_eval: per-walker theory rows needed (ld_walker != 0)");
+    if (ld_field < t->lmax + 1) fail(CMBL_ERR_ARG, "cmbt_eval: ld_field %lld below lmax + 1 = %d", ld_field, t->lmax + 1);
+    TheoryCalcArgs a{};
+    a.meta = t->meta.as<double>();
+    a.pidx = t->pidx_d.as<int>();
+    a.fields = t->fields_d.as<int>();
+    a.expo = t->expo.as<unsigned long long>();
+    a.coef = t->coef.as<double>();
+    a.n_in = t->n_in;
+    a.K = t->K;
+    a.Kp = t->Kp;
+    a.lmax = t->lmax;
+    a.Lp = t->Lp;
+    a.ntl = t->Lp / TC_TN;
+    a.W = W;
+    a.P = P;
+    a.ld = ld;
+    a.dl = dl;
+    a.ld_field = ld_field;
+    a.ld_walker = ld_walker;
+    a.fail = fail_flags;
+    const dim3 grid(t->n_fields * a.ntl, (W + TC_TW - 1) / TC_TW);
+    timed_launch("theory_calc_kernel", stream, [&](hipEvent_t e0, hipEvent_t e1) {
+        hipExtLaunchKernelGGL(theory_calc_kernel, grid, dim3(TC_THREADS), tc_lds_bytes(t->Kp), stream, e0, e1, 0, a);
+    });
+    HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace cmamd

@@ -126,6 +126,16 @@ class BatchedMCMC:
 
     set_drag_theory = set_trial_theory
 
+    def set_theory_calculator(self, calc):
+        """calc: cosmomc_amd.theory.PolynomialTheory, or None to remove it.  With
+        it, step_theory, step_drag and refresh_theory called with
+        theory_fn=None take the trial theory from the calculator on the device
+        (cmbs_set_theory_calculator): no host callback, every step queued at
+        once; a trial outside the calculator's box is rejected like one
+        outside the bounds.  Not part of save_state: set it again on resume."""
+        self._calc = calc                            # not owned by the library: keep it alive
+        self._check(N.lib().cmbs_set_theory_calculator(self._h, None if calc is None else calc.handle))
+
     def _theory_cb(self, theory_fn):
         import torch
         if theory_fn is None:
@@ -143,7 +153,9 @@ class BatchedMCMC:
 
     def step_theory(self, n_steps: int = 1, theory_fn=None, stream=None):
         """n_steps full GetNewSample steps (slow and fast proposals) with the
-        theory at every trial point from theory_fn(P_trial [num_params, W])."""
+        theory at every trial point from theory_fn(P_trial [num_params, W]),
+        or, with theory_fn None, from the calculator of set_theory_calculator
+        (then every step is queued without a host call)."""
         if stream is None:
             stream = N.current_stream_ptr()
         cb = self._theory_cb(theory_fn)
@@ -153,16 +165,18 @@ class BatchedMCMC:
         """n_steps TFastDraggingSampler_GetNewSample calls (MCMC.f90:338-452).
 
         theory_fn(P_end) -> None fills every end-theory buffer (set_drag_theory)
-        for the proposed points P_end, a cuda tensor view [num_params, W]."""
+        for the proposed points P_end, a cuda tensor view [num_params, W];
+        None: the calculator of set_theory_calculator fills them."""
         if stream is None:
             stream = N.current_stream_ptr()
         cb = self._theory_cb(theory_fn)
         self._check(N.lib().cmbs_step_drag(self._h, n_steps, dragging_steps, cb, None, stream))
 
-    def refresh_theory(self, theory_fn, stream=None):
+    def refresh_theory(self, theory_fn=None, stream=None):
         """After load_state of a run that moved slow parameters: theory_fn(P
         [num_params, W]) fills the trial-theory buffers at the current points,
-        which become the walkers' theory (cmbs_refresh_theory)."""
+        which become the walkers' theory (cmbs_refresh_theory).  theory_fn
+        None: the theory calculator (set_theory_calculator)."""
         if stream is None:
             stream = N.current_stream_ptr()
         cb = self._theory_cb(theory_fn)

@@ -20,6 +20,9 @@
  *                        (source/CMB.f90:305-329; called from calclike.f90:380)
  *   cmbl_clik_compute_batch  clik_lnlike packing (source/cliklike.f90:129-170) routed
  *                        to the native kernel; returns +lnL like clik_compute
+ *   cmbt_*               the calculator object's theory at a slow point, as a polynomial
+ *                        response surface of D_l (the slot of source/Calculator_PICO.f90;
+ *                        error = 1 outside the box -> logZero, calclike.f90:308-313)
  *   cmbs_*               BlockedProposer (source/propose.f90:53-298) + Metropolis
  *                        (source/MCMC.f90:119-335) + GetLogLike bounds/priors/temperature
  *                        (source/calclike.f90:82-151), batched over W independent chains
@@ -263,6 +266,64 @@ int  cmbs_step_theory(cmbs_t *s, int n_steps, cmbs_theory_fn theory_fn, void *us
  * terms stay as saved (not re-evaluated): theory_fn must reproduce the theory
  * the run had at those points. */
 int  cmbs_refresh_theory(cmbs_t *s, cmbs_theory_fn theory_fn, void *user, void *stream);
+
+/* ------------------------------------------------------------------ */
+/* Polynomial theory calculator: the theory at a slow point from a response
+ * surface of D_l, evaluated on the device (the place the reference gives its
+ * calculator object; Calculator_PICO.f90 is its polynomial emulator, whose
+ * error = 1 outside the training box becomes logZero, calclike.f90:308-313).
+ *
+ *   x_i      = (P[param_index_i] - center_i) / scale_i
+ *   basis_k  = prod_i x_i^exponents[k][i]   (from 1.0, i ascending, every power
+ *              by repeated multiplication)
+ *   dl[w*ld_walker + fields[j]*ld_field + l] = sum_k basis_k(w) * coef[k][j][l],
+ *              l = 0..lmax, fused multiply-adds in ascending k from +0.0;
+ *              nothing else in the buffer is written
+ * Walker w is valid iff every input has lo_i <= P_i <= hi_i (equality passes,
+ * NaN fails: the sampler's own bound test, calclike.f90:97-109).  A walker
+ * that is not is still evaluated, at its inputs clamped into the box (a NaN
+ * first replaced by center_i), so the buffer never holds junk.  A walker's
+ * result does not depend on W, on its place in the batch or on the strides. */
+typedef struct cmbt cmbt_t;
+typedef struct {
+    int n_in;                 /* 1..16 input parameters */
+    const int *param_index;   /* n_in, 1-based into P */
+    const double *center, *scale;   /* x_i = (P_i - center_i) / scale_i, scale_i != 0 */
+    const double *lo, *hi;    /* validity box on the raw P_i, lo_i <= hi_i */
+    int n_terms;              /* 1..256 monomials */
+    const int *exponents;     /* n_terms x n_in, row-major, each row's sum <= 4 (PICO's order) */
+    int n_fields;             /* 1..CMBL_NFIELDS */
+    const int *fields;        /* field indices 0..9 (TT=0 ... PP=9), no repeats */
+    int lmax;
+    const double *coef;       /* host, [n_terms][n_fields][lmax+1], l from 0 */
+} cmbt_config_t;
+/* Copies every table (the coefficients to the device); CMBL_ERR_ARG for a
+ * count outside its range, an exponent row above order 4, a zero scale,
+ * lo > hi, or a field index outside 0..9 or repeated. */
+int  cmbt_create(const cmbt_config_t *cfg, cmbt_t **out, char *errbuf, size_t errlen);
+void cmbt_destroy(cmbt_t *t);
+const char *cmbt_last_error(const cmbt_t *t);
+/* One launch, asynchronous on `stream`, for W points:
+ *   P     device rows [num_params][ld], walker-minor: what cmbs_theory_fn receives
+ *   dl    a theory buffer laid out as for cmbl_loglike_batch
+ *   fail  device int[W], 1 for a walker outside the box, else 0; or NULL
+ * CMBL_ERR_ARG for a param_index outside 1..num_params, ld < W,
+ * ld_walker == 0 or ld_field < lmax + 1. */
+int  cmbt_eval(cmbt_t *t, int W, const double *P, long long ld, int num_params,
+               double *dl, long long ld_field, long long ld_walker, int *fail, void *stream);
+/* The calculator as the sampler's theory source: with theory_fn == NULL,
+ * cmbs_step_theory and cmbs_step_drag evaluate it at the trial rows into every
+ * distinct trial-theory buffer (cmbs_set_trial_theory), one launch each and
+ * no host call or synchronisation inside the step loop, so all n_steps are
+ * queued at once.  A trial outside the calculator's box has -lnL = logZero,
+ * exactly as one outside the sampler's bounds (in a drag, such an end point
+ * aborts the drag, MCMC.f90:370-374).  cmbs_refresh_theory evaluates it at
+ * the current points and returns CMBL_ERR_NUMERIC, the walker theory rows
+ * untouched, if any lies outside the box.  A non-NULL theory_fn still takes
+ * precedence.  NULL removes the calculator.  Not owned: it must outlive the
+ * sampler's use of it, and it is not part of the cmbs_save_state image (a
+ * resumed run sets it again). */
+int  cmbs_set_theory_calculator(cmbs_t *s, cmbt_t *calc);
 
 /* Execution tuning (no reference counterpart; results are unchanged): split the
  * walkers into n_groups 64-aligned slices, each stepped on an internal stream
