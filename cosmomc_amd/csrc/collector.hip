@@ -337,15 +337,17 @@ __global__ void window_first_kernel(int W, const int *samp, int samp_cap, const 
     atomicMin(&out[0], samp[(size_t)((start[w] + cnt / 2 - 1) % samp_cap) * W + w]);
 }
 
-static void check_window_in_ring(cmbs *s) {
+// On the caller's stream, behind its pending collector_add / collector_thin
+// (a side stream does not synchronise with the null stream).
+static void check_window_in_ring(cmbs *s, hipStream_t st) {
     auto &c = s->coll;
-    const int init[2] = {0x7fffffff, 0x7fffffff};
-    HIP_CHECK(hipMemcpy(c.flag.p, init, 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(window_first_kernel, dim3((s->W + 255) / 256), dim3(256), 0, 0, s->W, c.samp.as<int>(), c.cap,
+    HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c.flag.p), 0x7fffffff, 2, st));
+    hipLaunchKernelGGL(window_first_kernel, dim3((s->W + 255) / 256), dim3(256), 0, st, s->W, c.samp.as<int>(), c.cap,
                        cstate(s, 0), cstate(s, 1), c.flag.as<int>());
     HIP_CHECK(hipGetLastError());
     int r[2];
-    HIP_CHECK(hipMemcpy(r, c.flag.p, 8, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpyAsync(r, c.flag.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
     if (r[1] < 2) fail(CMBL_ERR_ARG, "a walker has %d samples: too few for a window", r[1]);
     if (s->hist_count - r[0] > s->hist_cap)
         fail(CMBL_ERR_ARG, "a window starts at history step %d, no longer in the ring (count %d, capacity %d): "
@@ -358,7 +360,7 @@ void chain_moments_launch(const double *means, const double *covs, int W, int n,
 void sampler_collector_moments(cmbs *s, const double *gmean, double *out, hipStream_t stream) {
     auto &c = s->coll;
     if (!c.enabled) fail(CMBL_ERR_ARG, "collector not enabled");
-    if (!gmean) check_window_in_ring(s);
+    if (!gmean) check_window_in_ring(s, stream);
     const int n = s->n_used;
     s->mom.grow((size_t)s->W * (n + n * n) * 8);
     double *means = s->mom.as<double>(), *covs = means + (size_t)s->W * n;
@@ -388,7 +390,7 @@ void sampler_collector_limits(cmbs *s, const int *params, int ncheck, double lim
     if (ncheck <= 0) return;
     for (int k = 0; k < ncheck; k++)
         if (params[k] < 0 || params[k] >= s->n_used) fail(CMBL_ERR_ARG, "limit parameter %d out of range", params[k]);
-    check_window_in_ring(s);
+    check_window_in_ring(s, stream);
     c.steps.grow((size_t)ncheck * 4);
     HIP_CHECK(hipMemcpyAsync(c.steps.p, params, (size_t)ncheck * 4, hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(coll_limits_kernel, dim3(s->W, ncheck), dim3(256), 0, stream, s->hist.as<double>(), s->hist_cap,
