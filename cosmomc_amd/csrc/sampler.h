@@ -146,11 +146,21 @@ struct TailWait {
     int ntiles;              // counters (the first launch of a call zeroes them)
 };
 
+// Where a likelihood reads its theory: field f of walker w at
+// dl + w * ld_walker + f * ld_field (ld_walker 0: one row for every walker).
+// Two likelihoods read the same theory when their views are equal.
+struct TheoryView {
+    const double *dl = nullptr;
+    long long ld_field = 0, ld_walker = 0;
+    bool operator==(const TheoryView &o) const {
+        return dl == o.dl && ld_field == o.ld_field && ld_walker == o.ld_walker;
+    }
+};
+
 struct LikeSlot {
     cmbl_t *like;
     std::vector<int> nidx;   // nuisance_indices, 0-based
-    const double *dl;
-    long long ld_field, ld_walker;
+    TheoryView th;           // the walkers' theory
 };
 
 }  // namespace cmamd
@@ -188,12 +198,11 @@ struct cmbs {
     cmamd::DevBuf ws_g[cmamd::MAXGROUPS];
     // fast dragging (cmbs_step_drag): scratch rows, second likelihood set, end-point theories
     cmamd::DevBuf drag_dd, drag_di, like_terms2;
-    cmamd::DevBuf like_ws2[cmamd::MAXLIKE];  // the fused likelihoods' workspaces for the start-point set (drag pairs)
+    cmamd::DevBuf like_ws2[cmamd::MAXLIKE];  // the fused likelihoods' workspaces for a drag's start-point set
     bool no_drag_pair = false;               // debug: the drag's two evaluation sets one after the other
     bool drag_hbm = false;                   // debug: drag_kernel on the HBM state (cmamd_debug_drag_hbm)
     cmamd::DevBuf nuis_bufs2[cmamd::MAXLIKE];
-    struct EndTheory { double *dl = nullptr; long long ld_field = 0, ld_walker = 0; };
-    EndTheory end_theory[cmamd::MAXLIKE];
+    cmamd::TheoryView end_theory[cmamd::MAXLIKE];   // the trial-theory buffers (cmbs_set_trial_theory)
     long long num_drag = 0;
     // theory calculator (cmbs_set_theory_calculator; not owned): with no theory
     // function, the trial theories come from it, and calc_fail [ld] holds the

@@ -18,13 +18,16 @@
 // independent coalesced loads, runs the chain out of LDS and writes back.
 //
 // This file holds every kernel entry point of the chain, then the host side:
-// set-up, likelihood evaluation, the step schedules.  The device bodies are
+// set-up and the fast-step schedules.  The device bodies are
 // headers included inside namespace cmamd, in this order: mhrng.h (RANMAR),
 // mhpropose.h (walker view, proposer, target), mhstage.h (LDS staging),
 // mhwait.h (the unified launch's arrival and wait), mhlean.h and mhbody.h (the
 // lean and the general chain), mhstep.h (the unified launch's roles), mhrot.h
-// (deferred rotations), mhdrag.h (fast dragging).  The history statistics are
-// history.hip, the state image state.hip.
+// (deferred rotations), mhdrag.h (fast dragging).  Two host-side headers
+// follow in the same way: likeeval.h (the likelihoods' evaluation at a set of
+// points) and slowstep.h (cmbs_step_theory, cmbs_step_drag and
+// cmbs_refresh_theory).  The history statistics are history.hip, the state
+// image state.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -666,7 +669,7 @@ static void setup_fusion(cmbs *s) {
             if (sparse(i) || sparse(j)) continue;
             const LikeSlot &P = s->likes[i], &C = s->likes[j];
             s->tp_why = std::max(s->tp_why, 2);
-            if (P.dl != C.dl || P.ld_field != C.ld_field || P.ld_walker != C.ld_walker) continue;
+            if (!(P.th == C.th)) continue;
             WinStage sp, sc;
             s->tp_why = std::max(s->tp_why, 3);
             if (!P.like->like->window_stage(sp) || sp.kind != 1) continue;
@@ -725,7 +728,7 @@ void sampler_add_likelihood(cmbs *s, cmbl_t *like, const int *nuisance_indices, 
     }
     if ((int)s->likes.size() >= MAXLIKE) fail(CMBL_ERR_ARG, "at most %d likelihoods per sampler", MAXLIKE);
     const int li = (int)s->likes.size();
-    s->likes.push_back({like, nidx, dl, ld_field, ld_walker});
+    s->likes.push_back({like, nidx, TheoryView{dl, ld_field, ld_walker}});
     // the index list joins the int table (LDS-staged with the proposer tables)
     s->dc.like_nidx[li] = (int)s->h_tab_i.size();
     s->h_tab_i.insert(s->h_tab_i.end(), nidx.begin(), nidx.end());
@@ -811,198 +814,11 @@ static void set_change_mask(cmbs *s) {
         s->like_outc[li].alloc((size_t)W * 8);
         s->like_nuisc[li].alloc((size_t)W * nn * 8 + (size_t)ld * 4);   // + the slot -> walker map
         s->dc.like_out[li] = s->like_outc[li].as<double>();
-        if (s->likes[li].ld_walker != 0) s->like_dlc[li].alloc((size_t)W * s->likes[li].ld_walker * 8);
+        if (s->likes[li].th.ld_walker != 0) s->like_dlc[li].alloc((size_t)W * s->likes[li].th.ld_walker * 8);
     }
 }
 
-// the likelihoods of a masked step: compaction of the sparse likelihoods'
-// changed walkers, then every likelihood (sparse ones on the compacted slots)
-// a deferrable likelihood's evaluation for the accepting mh_kernel that follows:
-// the launches up to the quadratic form's partials, recorded in s->dc.def_*
-static bool is_deferred(const cmbs *s, size_t i) {
-    for (int q : s->defer_likes)
-        if (q == (int)i) return true;
-    return false;
-}
-
-static void record_deferred(cmbs *s, size_t i, const QFDeferred &d) {
-    const int p = s->pending_def++;
-    s->dc.def_like[p] = (int)i;
-    s->dc.def_items[p] = d.n_items;
-    s->dc.def_part[p] = d.partial;
-    s->dc.def_add[p] = d.addend;
-}
-
-// the fused window pass over the whole walker set (eval_likes_fused)
-static bool fused(const cmbs *s, size_t i) {
-    return s->tpass && ((int)i == s->tp_like[0] || (int)i == s->tp_like[1]);
-}
-
-// the pass over theory rows dl (the walkers' own, or the drag's end points)
-// with nuisance slices nuis[i] of likelihood i
-static void launch_tpass(cmbs *s, hipStream_t stream, const double *dl, long long ld_field, long long ld_walker,
-                         double *const *nuis) {
-    TPOut o[2];
-    for (int k = 0; k < 2; k++) {
-        const int i = s->tp_like[k];
-        const WinStage &st = s->tp_stage[k];
-        Like &L = *s->likes[i].like->like;
-        o[k] = TPOut{st.kind, st.cal_index, st.ld, 0, L.window_out(s->like_ws[i].p, s->W), st.X, nuis[i],
-                     (long long)std::max(1, L.n_nuis)};
-    }
-    s->tpass->launch(dl, ld_field, ld_walker, o, s->W, stream);
-}
-
-static void launch_tpass(cmbs *s, hipStream_t stream) {
-    const LikeSlot &P = s->likes[s->tp_like[0]];
-    launch_tpass(s, stream, P.dl, P.ld_field, P.ld_walker, s->dc.like_nuis);
-}
-
-// The fused pass's two tails as one launch: when one fused likelihood is
-// deferred and its quadratic form carries co-runs (plik_lite) and the other's
-// whole after-window stage is a small chi^2 (Planck lensing), the chi^2's
-// workgroups run in the quadratic form's launch (quadform_corun) and its term
-// lands in its like_terms row as before.  The carrier and the carried index
-// for this step, or -1, -1.
-struct Corun {
-    int carrier = -1, carried = -1;
-    SmallGaussLaunch a{};
-};
-
-static Corun plan_corun(cmbs *s, bool defer) {
-    Corun c;
-    if (!defer || !s->tpass || s->no_corun) return c;
-    for (int k = 0; k < 2; k++) {
-        const int h = s->tp_like[k], o = s->tp_like[1 - k];
-        Like &H = *s->likes[h].like->like;
-        Like &O = *s->likes[o].like->like;
-        if (!is_deferred(s, h) || !H.accepts_corun()) continue;
-        if (O.corun_small(c.a, s->W, s->dc.like_nuis[o], O.n_nuis, s->like_terms.as<double>() + o * (size_t)s->dc.ld,
-                          s->like_ws[o].p)) {
-            c.carrier = h;
-            c.carried = o;
-            return c;
-        }
-    }
-    return c;
-}
-
-// the rest of a fused likelihood after the pass: deferred or into its like_terms row
-static void eval_after_window(cmbs *s, size_t i, bool defer, hipStream_t stream, const Corun &co) {
-    if ((int)i == co.carried) return;   // inside the carrier's launch
-    Like &L = *s->likes[i].like->like;
-    const bool d = defer && is_deferred(s, i);
-    const QFDeferred q = L.after_window(s->W, s->dc.like_nuis[i], L.n_nuis,
-                                        d ? nullptr : s->like_terms.as<double>() + i * (size_t)s->dc.ld,
-                                        s->like_ws[i].p, stream, d, (int)i == co.carrier ? &co.a : nullptr);
-    if (d) record_deferred(s, i, q);
-}
-
-static bool eval_deferred(cmbs *s, size_t i, const double *nuis, hipStream_t stream) {
-    if (!is_deferred(s, i)) return false;
-    auto &l = s->likes[i];
-    const QFDeferred d = l.like->like->loglike_batch_deferred(s->W, l.dl, l.ld_field, l.ld_walker, nuis,
-                                                              l.like->like->n_nuis, s->like_ws[i].p, stream);
-    record_deferred(s, i, d);
-    return true;
-}
-
-static void eval_likes_masked(cmbs *s, hipStream_t stream, bool defer = false) {
-    SparseSet ss{};
-    const int ns = (int)s->sparse_likes.size();
-    for (int b = 0; b < ns; b++) {
-        const int li = s->sparse_likes[b];
-        const int nn = s->likes[li].like->like->n_nuis;
-        ss.like[b] = li;
-        ss.nn[b] = nn;
-        ss.nuisc[b] = s->like_nuisc[li].as<double>();
-        ss.map[b] = reinterpret_cast<int *>(ss.nuisc[b] + (size_t)s->W * std::max(1, nn));
-    }
-    int *cnt = s->like_cnt.as<int>();
-    hipLaunchKernelGGL(like_compact_kernel, dim3(ns), dim3(1024), 0, stream, s->dc, ss, cnt);
-    HIP_CHECK(hipGetLastError());
-    if (s->tpass) launch_tpass(s, stream);   // the fused likelihoods are dense (setup_fusion)
-    const Corun co = plan_corun(s, defer);
-    for (size_t i = 0; i < s->likes.size(); i++) {
-        auto &l = s->likes[i];
-        const int nn = l.like->like->n_nuis;
-        int b = -1;
-        for (int q = 0; q < ns; q++)
-            if (ss.like[q] == (int)i) b = q;
-        if (b < 0) {
-            if (fused(s, i)) {
-                eval_after_window(s, i, defer, stream, co);
-                continue;
-            }
-            if (defer && eval_deferred(s, i, s->dc.like_nuis[i], stream)) continue;
-            l.like->like->loglike_batch(s->W, l.dl, l.ld_field, l.ld_walker, s->dc.like_nuis[i], nn,
-                                        s->like_terms.as<double>() + i * (size_t)s->dc.ld, s->ws.p, stream);
-            continue;
-        }
-        const double *dl = l.dl;
-        if (l.ld_walker != 0) {
-            double *dlc = s->like_dlc[i].as<double>();
-            hipLaunchKernelGGL(gather_theory_kernel, dim3(s->W), dim3(256), 0, stream, l.dl, l.ld_walker,
-                               theory_extent(*l.like->like, l.ld_field), (const int *)ss.map[b], (const int *)(cnt + b),
-                               dlc);
-            HIP_CHECK(hipGetLastError());
-            dl = dlc;
-        }
-        l.like->like->loglike_batch_sparse(s->W, dl, l.ld_field, l.ld_walker, ss.nuisc[b], nn,
-                                           s->like_outc[i].as<double>(), s->ws.p, stream, cnt + b);
-    }
-}
-
-// likelihood terms of walkers [g0, g1) at their trial points
-// defer: the accepting mh_kernel launched next finishes the deferrable
-// likelihoods (all walkers, one group)
-static void eval_likes(cmbs *s, hipStream_t stream, bool gather, int g0, int g1, void *ws, bool defer = false) {
-    const int Wg = g1 - g0;
-    if (defer && (g0 != 0 || g1 != s->W)) fail(CMBL_ERR_ARG, "internal: deferred evaluation of a walker group");
-    const size_t nl = s->likes.size();
-    const bool fuse = s->tpass && g0 == 0 && g1 == s->W;
-    if (fuse) {   // every nuisance slice first: the pass reads both likelihoods'
-        if (gather)
-            for (size_t i = 0; i < nl; i++) {
-                const int nn = s->likes[i].like->like->n_nuis;
-                hipLaunchKernelGGL(gather_nuis, dim3((s->W + 255) / 256), dim3(256), 0, stream,
-                                   s->dc.sd + (size_t)s->dc.rows.T * s->dc.ld, s->W, s->dc.ld,
-                                   s->dc.tab_i + s->dc.like_nidx[i], nn, s->dc.like_nuis[i]);
-                HIP_CHECK(hipGetLastError());
-            }
-        gather = false;
-        launch_tpass(s, stream);
-    }
-    const Corun co = fuse ? plan_corun(s, defer) : Corun{};
-    // the likelihoods run in order on the caller's stream: side by side on forked
-    // streams the memory-bound likelihood kernels slow each other more than they
-    // overlap (MI355X, W = 1024, plik_lite + lensing: 77.1 vs 71.9 us/step; the
-    // binning kernel alone 12.5 -> 26.2 us next to the lensing windows).  Even
-    // the fused pass's two tails (quadratic form and the lensing chi^2, 13.6 and
-    // 7.1 us) lose: with the chi^2 on a side stream forked and joined by events
-    // the step took 87.5 instead of 63.3 us (round 2).  They share one launch
-    // instead (plan_corun): 15.4 us against 13.5 + 4.6 (round 3)
-    for (size_t i = 0; i < nl; i++) {
-        hipStream_t st = stream;
-        auto &l = s->likes[i];
-        const int nn = l.like->like->n_nuis;
-        double *nb = s->dc.like_nuis[i];
-        if (gather) {   // mh_kernel scatters the nuisance slices itself on every step
-            hipLaunchKernelGGL(gather_nuis, dim3((s->W + 255) / 256), dim3(256), 0, st,
-                               s->dc.sd + (size_t)s->dc.rows.T * s->dc.ld, s->W, s->dc.ld,
-                               s->dc.tab_i + s->dc.like_nidx[i], nn, nb);
-            HIP_CHECK(hipGetLastError());
-        }
-        if (fuse && fused(s, i)) {
-            eval_after_window(s, i, defer, st, co);
-            continue;
-        }
-        if (defer && eval_deferred(s, i, nb, st)) continue;
-        l.like->like->loglike_batch(Wg, l.dl + (size_t)g0 * l.ld_walker, l.ld_field, l.ld_walker,
-                                    nb + (size_t)g0 * nn, nn, s->like_terms.as<double>() + i * (size_t)s->dc.ld + g0,
-                                    ws, st);
-    }
-}
+#include "likeeval.h"
 
 // the history ring slots of the next recorded step (none when history is off)
 struct HistRow {
@@ -1101,7 +917,7 @@ static bool bin_setup(cmbs *s, int fast_only, PlikBinArgs &pb) {
         return false;
     const LikeSlot &L = s->likes[0];
     WinStage st;
-    if (!L.like->like->bin_args(pb, L.dl, L.ld_field, L.ld_walker) || !L.like->like->window_stage(st) ||
+    if (!L.like->like->bin_args(pb, L.th.dl, L.th.ld_field, L.th.ld_walker) || !L.like->like->window_stage(st) ||
         st.cal_index < 0)
         return false;
     const size_t need = (size_t)QuadForm::wpad(s->W) * pb.Np * 8;
@@ -1256,7 +1072,8 @@ void sampler_set_start(cmbs *s, const double *P0, hipStream_t stream) {
                                (size_t)s->W * 8, (size_t)s->W * 8, s->np, hipMemcpyHostToDevice, stream));
     // t is pageable and local: the copy must be complete before anything below can throw and unwind it
     HIP_CHECK(hipStreamSynchronize(stream));
-    eval_likes(s, stream, true, 0, s->W, s->ws.p);
+    gather_trial_nuis(s, stream);
+    eval_likes(s, stream, 0, s->W, s->ws.p);
     hipLaunchKernelGGL(start_kernel, dim3((s->W + 255) / 256), dim3(256), 0, stream, s->dc);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(stream));
@@ -1282,7 +1099,7 @@ static bool tail_setup(cmbs *s, int fast_only) {
         (s->dc.rot_defer && s->rot_fast_any) || s->likes.size() != 2)
         return false;
     {
-        const LikeSlot &P = s->likes[s->tp_like[0]];
+        const TheoryView &P = s->likes[s->tp_like[0]].th;
         if (!s->tpass->vec_ok(P.dl, P.ld_field, P.ld_walker)) return false;
     }
     if (s->tail_ready == s->W) return true;
@@ -1387,7 +1204,7 @@ static StepTail make_tail(cmbs *s, int rd, int wr) {
                          (long long)std::max(1, L.n_nuis)};
         }
         t.tp = s->tpass->dev_args(o, W);
-        const LikeSlot &P = s->likes[s->tp_like[0]];
+        const TheoryView &P = s->likes[s->tp_like[0]].th;
         t.dl = P.dl;
         t.ld_field = P.ld_field;
         t.ld_walker = P.ld_walker;
@@ -1516,16 +1333,11 @@ void sampler_step(cmbs *s, int n_steps, int fast_only, hipStream_t stream) {
         return;
     }
     if (G == 1) {
-        const bool m = s->mask_on;
-        launch_mh(s, false, true, fast_only, HistRow{}, stream, 0, s->W, m);
-        if (m) eval_likes_masked(s, stream, true);
-        else eval_likes(s, stream, false, 0, s->W, s->ws.p, true);
-        for (int k = 1; k < n_steps; k++) {
-            launch_mh(s, true, true, fast_only, next_hist(s), stream, 0, s->W, m);
-            if (m) eval_likes_masked(s, stream, true);
-            else eval_likes(s, stream, false, 0, s->W, s->ws.p, true);
+        for (int k = 0; k <= n_steps; k++) {
+            const HistRow row = k > 0 ? next_hist(s) : HistRow{};
+            launch_mh(s, k > 0, k < n_steps, fast_only, row, stream, 0, s->W, s->mask_on);
+            if (k < n_steps) eval_trial_likes(s, stream, true);
         }
-        launch_mh(s, true, false, fast_only, next_hist(s), stream, 0, s->W, m);
         return;
     }
     // groups are independent chains: fork from the caller's stream, issue the
@@ -1543,9 +1355,9 @@ void sampler_step(cmbs *s, int n_steps, int fast_only, hipStream_t stream) {
         for (int g = 0; g < G; g++) {
             const int g0 = s->grp0[g], g1 = s->grp0[g + 1];
             launch_mh(s, k > 0, k < n_steps, fast_only, row, whole ? stream : s->streams[g], g0, g1);
-            if (k < n_steps && !whole) eval_likes(s, s->streams[g], false, g0, g1, s->ws_g[g].p);
+            if (k < n_steps && !whole) eval_likes(s, s->streams[g], g0, g1, s->ws_g[g].p);
         }
-        if (k < n_steps && whole) eval_likes(s, stream, false, 0, s->W, s->ws.p);
+        if (k < n_steps && whole) eval_likes(s, stream, 0, s->W, s->ws.p);
     }
     for (int g = 0; g < G; g++) {
         HIP_CHECK(hipEventRecord(s->events[g], s->streams[g]));
@@ -1553,376 +1365,7 @@ void sampler_step(cmbs *s, int n_steps, int fast_only, hipStream_t stream) {
     }
 }
 
-void sampler_set_trial_theory(cmbs *s, int like_index, double *dl_end, long long ld_field, long long ld_walker) {
-    if (like_index < 0 || like_index >= (int)s->likes.size()) fail(CMBL_ERR_ARG, "no likelihood %d", like_index);
-    auto &e = s->end_theory[like_index];
-    e.dl = dl_end;
-    e.ld_field = ld_field;
-    e.ld_walker = ld_walker;
-}
-
-// likelihood terms of set 1 (T rows, end theory) or set 2 (T2 rows, walker theory)
-static void eval_likes_drag(cmbs *s, int set, hipStream_t stream) {
-    // the fused window pass when both likelihoods read one buffer of this set
-    bool fuse = false;
-    if (s->tpass) {
-        const int p = s->tp_like[0], c = s->tp_like[1];
-        if (set == 1) {
-            const auto &a = s->end_theory[p], &b = s->end_theory[c];
-            fuse = a.dl == b.dl && a.ld_field == b.ld_field && a.ld_walker == b.ld_walker;
-            if (fuse) launch_tpass(s, stream, a.dl, a.ld_field, a.ld_walker, s->dc.like_nuis);
-        } else {
-            double *nb2[MAXLIKE] = {};
-            for (size_t i = 0; i < s->likes.size(); i++) nb2[i] = s->nuis_bufs2[i].as<double>();
-            const LikeSlot &P = s->likes[p];
-            fuse = true;
-            launch_tpass(s, stream, P.dl, P.ld_field, P.ld_walker, nb2);
-        }
-    }
-    for (size_t i = 0; i < s->likes.size(); i++) {
-        auto &l = s->likes[i];
-        const int nn = l.like->like->n_nuis;
-        const double *dl = l.dl;
-        long long ldf = l.ld_field, ldw = l.ld_walker;
-        double *nb = s->dc.like_nuis[i];
-        double *out = s->like_terms.as<double>() + i * (size_t)s->dc.ld;
-        if (set == 1) {
-            dl = s->end_theory[i].dl;
-            ldf = s->end_theory[i].ld_field;
-            ldw = s->end_theory[i].ld_walker;
-        } else {
-            nb = s->nuis_bufs2[i].as<double>();
-            out = s->like_terms2.as<double>() + i * (size_t)s->dc.ld;
-        }
-        if (fuse && fused(s, i)) {
-            l.like->like->after_window(s->W, nb, nn, out, s->like_ws[i].p, stream, false);
-            continue;
-        }
-        l.like->like->loglike_batch(s->W, dl, ldf, ldw, nb, nn, out, s->ws.p, stream);
-    }
-}
-
-// drag_staged_kernel's LDS image (0 when it would not fit a CU's 160 KB)
-static size_t drag_lds_bytes(const cmbs *s) {
-    const DevCfg &d = s->dc;
-    const int nd_st = d.stage_R ? d.rows.ND : d.rows.ND - d.rows.RR;
-    const int ni_st = d.stage_cyc ? d.rows.NI : d.rows.CYC;
-    const int ntd = d.stage_cov ? d.tl.n_dbl : d.tl.covinv;
-    const int nlk = (d.n_like + 1) & ~1, ndd = (drag_rows(d) + 1) & ~1;
-    const size_t b = (size_t)(nd_st + ndd + 2 * nlk) * MB * 8 + (size_t)((ntd + 31) & ~31) * 8 +
-                     (size_t)(ni_st + 4 + d.all_n) * MB * 4 + (size_t)((d.tl.n_int + 63) & ~63) * 4;
-    return b <= 160 * 1024 ? b : 0;
-}
-
-template <int STAGE>
-static void launch_drag(cmbs *s, const DragCfg &g, const HistRow &row, hipStream_t stream) {
-    const size_t lds = drag_lds_bytes(s);
-    timed_launch("drag_kernel", stream, [&](hipEvent_t e0, hipEvent_t e1) {
-        if (lds && !s->drag_hbm)
-            hipExtLaunchKernelGGL(drag_staged_kernel<STAGE>, dim3((s->W + MB - 1) / MB), dim3(MH_THREADS), lds, stream,
-                                  e0, e1, 0, s->dc, g, row.p, row.t);
-        else
-            hipExtLaunchKernelGGL(drag_kernel<STAGE>, dim3((s->W + 63) / 64), dim3(64), 0, stream, e0, e1, 0, s->dc,
-                                  g, row.p, row.t);
-    });
-    HIP_CHECK(hipGetLastError());
-}
-
-// Both evaluation sets of a drag's interpolation step (the end points T with
-// the end theories, the start points T2 with the walkers' theories) as two
-// launches instead of eight: the fused window pass over both theory sets
-// (theory_window_pair, which also zeroes the tickets), then plik_lite's two
-// in-launch-combined quadratic forms with both lensing chi^2s riding along
-// (launch_qf_pair).  Set 2 works in its own workspaces (like_ws2).  False when
-// the sets cannot be fused (then eval_likes_drag runs each).
-static bool eval_likes_drag_pair(cmbs *s, hipStream_t stream, bool both = true) {
-    if (!s->tpass || s->no_drag_pair) return false;
-    int kq = -1, kg = -1;
-    for (int k = 0; k < 2; k++) (s->tp_stage[k].kind == 1 ? kq : kg) = k;
-    if (kq < 0 || kg < 0) return false;
-    const int qi = s->tp_like[kq], gi = s->tp_like[kg];
-    const auto &ea = s->end_theory[qi], &eb = s->end_theory[gi];
-    if (ea.dl != eb.dl || ea.ld_field != eb.ld_field || ea.ld_walker != eb.ld_walker) return false;
-    const LikeSlot &P = s->likes[qi];
-    if (!s->tpass->vec_ok(ea.dl, ea.ld_field, ea.ld_walker) || !s->tpass->vec_ok(P.dl, P.ld_field, P.ld_walker))
-        return false;
-    const int W = s->W;
-    for (int k = 0; k < 2; k++) {
-        const int i = s->tp_like[k];
-        const size_t need = s->likes[i].like->like->workspace_size(W);
-        if (s->like_ws2[i].bytes < need) s->like_ws2[i].alloc(need);
-    }
-    Like &Q = *s->likes[qi].like->like;
-    Like &G = *s->likes[gi].like->like;
-    QFSource qa, qb;
-    if (!Q.qf_source(qa, W, s->like_ws[qi].p) || !Q.qf_source(qb, W, s->like_ws2[qi].p)) return false;
-    SmallGaussLaunch ga{}, gb{};
-    const size_t ld = s->dc.ld;
-    double *t1 = s->like_terms.as<double>(), *t2 = s->like_terms2.as<double>();
-    if (!G.corun_small(ga, W, s->dc.like_nuis[gi], G.n_nuis, t1 + (size_t)gi * ld, s->like_ws[gi].p) ||
-        !G.corun_small(gb, W, s->nuis_bufs2[gi].as<double>(), G.n_nuis, t2 + (size_t)gi * ld, s->like_ws2[gi].p))
-        return false;
-    TPOut oa[2], ob[2];
-    for (int k = 0; k < 2; k++) {
-        const int i = s->tp_like[k];
-        const WinStage &st = s->tp_stage[k];
-        Like &L = *s->likes[i].like->like;
-        const long long ldn = std::max(1, L.n_nuis);
-        oa[k] = TPOut{st.kind, st.cal_index, st.ld, 0, L.window_out(s->like_ws[i].p, W), st.X, s->dc.like_nuis[i], ldn};
-        ob[k] = TPOut{st.kind, st.cal_index, st.ld, 0, L.window_out(s->like_ws2[i].p, W), st.X,
-                      s->nuis_bufs2[i].as<double>(), ldn};
-    }
-    s->tpass->launch_pair(ea.dl, ea.ld_field, ea.ld_walker, oa, qa.counters, both ? P.dl : nullptr, P.ld_field,
-                          P.ld_walker, ob, qb.counters, qa.n_counters, W, stream);
-    launch_qf_pair(qa, t1 + (size_t)qi * ld, both ? &qb : nullptr, t2 + (size_t)qi * ld, W, &ga, both ? &gb : nullptr,
-                   stream, "plik_quadform_pair");
-    for (size_t i = 0; i < s->likes.size(); i++) {   // any other likelihood, one set after the other
-        if (fused(s, i)) continue;
-        auto &l = s->likes[i];
-        const int nn = l.like->like->n_nuis;
-        const auto &e = s->end_theory[i];
-        l.like->like->loglike_batch(W, e.dl, e.ld_field, e.ld_walker, s->dc.like_nuis[i], nn, t1 + i * ld, s->ws.p,
-                                    stream);
-        if (both)
-            l.like->like->loglike_batch(W, l.dl, l.ld_field, l.ld_walker, s->nuis_bufs2[i].as<double>(), nn,
-                                        t2 + i * ld, s->ws.p, stream);
-    }
-    return true;
-}
-
-// Whether likelihood i's accepted-theory copy repeats an earlier likelihood's
-// (the same end and walker theory buffers and strides: fused likelihoods
-// usually read one): then it is skipped, the copy being idempotent
-static bool same_theory_swap(const cmbs *s, int i) {
-    const auto &e = s->end_theory[i];
-    const auto &l = s->likes[i];
-    for (int j = 0; j < i; j++) {
-        const auto &ej = s->end_theory[j];
-        const auto &lj = s->likes[j];
-        if (ej.dl == e.dl && ej.ld_walker == e.ld_walker && lj.dl == l.dl && lj.ld_walker == l.ld_walker &&
-            std::min(ej.ld_walker, lj.ld_walker) >= std::min(e.ld_walker, l.ld_walker))
-            return true;
-    }
-    return false;
-}
-
-// ---- theory calculator (cmbs_set_theory_calculator): the trial theories
-// without a theory function
-void sampler_set_theory_calculator(cmbs *s, cmbt *calc) {
-    s->calc = calc;
-    if (calc && !s->calc_fail.p) s->calc_fail.alloc((size_t)s->dc.ld * 4);
-}
-
-// the calculator at parameter rows Prows [np][ld] into every distinct
-// trial-theory buffer (one launch each), the walkers outside its box flagged
-// in calc_fail
-static void calc_trial_theory(cmbs *s, const double *Prows, hipStream_t stream) {
-    for (size_t i = 0; i < s->likes.size(); i++) {
-        const auto &e = s->end_theory[i];
-        bool seen = false;
-        for (size_t j = 0; j < i && !seen; j++) {
-            const auto &ej = s->end_theory[j];
-            seen = ej.dl == e.dl && ej.ld_field == e.ld_field && ej.ld_walker == e.ld_walker;
-        }
-        if (seen) continue;
-        theorycalc_eval(s->calc, s->W, Prows, (long long)s->dc.ld, s->np, e.dl, e.ld_field, e.ld_walker,
-                        s->calc_fail.as<int>(), stream);
-    }
-}
-
-// A trial outside the calculator's box: every likelihood term becomes logZero,
-// so target_like gives logZero as for a trial outside the sampler's bounds
-// (the calculator's error flag, calclike.f90:308-313)
-__global__ void calc_fail_terms(const int *__restrict__ flag, double *terms, int n_like, int W, size_t ld)
-{
-    const int w = blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= W || flag[w] == 0) return;
-    for (int l = 0; l < n_like; l++) terms[(size_t)l * ld + w] = LOGZERO;
-}
-
-static void apply_calc_fail(cmbs *s, hipStream_t stream) {
-    hipLaunchKernelGGL(calc_fail_terms, dim3((s->W + 255) / 256), dim3(256), 0, stream, s->calc_fail.as<int>(),
-                       s->like_terms.as<double>(), (int)s->likes.size(), s->W, (size_t)s->dc.ld);
-    HIP_CHECK(hipGetLastError());
-}
-
-void sampler_step_drag(cmbs *s, int n_steps, double dragging_steps, cmbs_theory_fn fn, void *user,
-                       hipStream_t stream) {
-    rot_schedule_unknown(s);           // the drag proposals move the blocks' loop indices
-    if (!s->started) fail(CMBL_ERR_ARG, "cmbs_set_start must be called before cmbs_step_drag");
-    check_theory_fresh(s);
-    if (n_steps <= 0) return;
-    if (s->fast_n == 0 || s->slow_n == 0) {   // MCMC.f90:351-354: plain Metropolis
-        sampler_step(s, n_steps, 0, stream);
-        return;
-    }
-    const int nl = (int)s->likes.size();
-    for (int i = 0; i < nl; i++)
-        if (!s->end_theory[i].dl) fail(CMBL_ERR_ARG, "dragging needs an end-point theory buffer for likelihood %d", i);
-    if (nl > 0 && !fn && !s->calc) fail(CMBL_ERR_ARG, "dragging with data likelihoods needs a theory function");
-    const size_t ld = s->dc.ld;
-    const int np = s->np;
-    if (!s->drag_dd.p) {
-        s->drag_dd.alloc((size_t)(3 * np + 4 + s->dc.max_blk + std::max<size_t>(1, s->likes.size())) * ld * 8);
-        s->drag_di.alloc((size_t)(1 + s->all_n) * ld * 4);
-        HIP_CHECK(hipMemset(s->drag_dd.p, 0, s->drag_dd.bytes));
-        HIP_CHECK(hipMemset(s->drag_di.p, 0, s->drag_di.bytes));
-        s->like_terms2.alloc(std::max<size_t>(1, s->likes.size()) * ld * 8);
-        HIP_CHECK(hipMemset(s->like_terms2.p, 0, s->like_terms2.bytes));
-        for (int i = 0; i < nl; i++)
-            s->nuis_bufs2[i].alloc((size_t)std::max(s->likes[i].like->like->n_nuis, 1) * s->W * 8);
-    }
-    DragCfg g{};
-    g.dd = s->drag_dd.as<double>();
-    g.di = s->drag_di.as<int>();
-    g.like_terms2 = s->like_terms2.as<double>();
-    for (int i = 0; i < nl; i++) g.like_nuis2[i] = s->nuis_bufs2[i].as<double>();
-    int interp = (int)std::lround(dragging_steps * s->fast_n) + 1;   // MCMC.f90:386
-    if (interp < 2) interp = 2;
-    g.interp = interp;
-    if (const size_t lds = drag_lds_bytes(s))
-        for (const void *k : {(const void *)drag_staged_kernel<0>, (const void *)drag_staged_kernel<1>,
-                              (const void *)drag_staged_kernel<2>})
-            HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    for (int step = 0; step < n_steps; step++) {
-        s->num_drag++;
-        if (s->num_drag % s->dc.oversample_fast != 0) {   // FastParameterSample (:357-361)
-            const bool m = s->mask_on;
-            launch_mh(s, false, true, 1, HistRow{}, stream, 0, s->W, m);
-            if (m) eval_likes_masked(s, stream);
-            else eval_likes(s, stream, false, 0, s->W, s->ws.p);
-            launch_mh(s, true, false, 1, next_hist(s), stream, 0, s->W, m);
-            continue;
-        }
-        g.istep = 0;
-        launch_drag<0>(s, g, HistRow{}, stream);
-        if (nl > 0) {
-            const double *Pend = s->dc.sd + (size_t)s->dc.rows.T * ld;
-            if (!fn) calc_trial_theory(s, Pend, stream);
-            else if (fn(user, s->W, Pend, (long long)ld, stream) != 0) fail(CMBL_ERR_ARG, "theory function failed");
-            if (!eval_likes_drag_pair(s, stream, false)) eval_likes_drag(s, 1, stream);
-            if (!fn) apply_calc_fail(s, stream);   // a flagged end point aborts its drag in stage 1
-        }
-        launch_drag<1>(s, g, HistRow{}, stream);
-        for (int is = 1; is <= interp - 1; is++) {
-            if (nl > 0 && !eval_likes_drag_pair(s, stream)) {
-                eval_likes_drag(s, 1, stream);
-                eval_likes_drag(s, 2, stream);
-            }
-            g.istep = is;
-            const HistRow row = is == interp - 1 ? next_hist(s) : HistRow{};
-            launch_drag<2>(s, g, row, stream);
-        }
-        s->theory_moved = s->theory_moved || nl > 0;
-        for (int i = 0; i < nl; i++) {               // accepted drags keep the end theory
-            const auto &e = s->end_theory[i];
-            const auto &l = s->likes[i];
-            const long long n = std::min(e.ld_walker, l.ld_walker) > 0 ? std::min(e.ld_walker, l.ld_walker)
-                                                                        : 10 * l.ld_field;
-            if (l.ld_walker == 0) fail(CMBL_ERR_ARG, "dragging needs per-walker theory rows (ld_walker > 0)");
-            if (same_theory_swap(s, i)) continue;
-            hipLaunchKernelGGL(drag_swap_theory, dim3(8, s->W), dim3(256), 0, stream, g.di, 4, s->W, e.dl,
-                               e.ld_walker, const_cast<double *>(l.dl), l.ld_walker, n);
-            HIP_CHECK(hipGetLastError());
-        }
-        // (every walker's dst is set again by the next drag's stage 0)
-    }
-}
-
-// full TMetropolisSampler_GetNewSample steps (MCMC.f90:269-307) with the
-// theory recomputed at every trial point: the caller's theory function fills
-// the trial-theory buffers, the likelihoods run on them, and accepted walkers
-// take the trial theory as their own
-static void swap_accepted_theory(cmbs *s, hipStream_t stream) {
-    const int *flag = s->dc.si + (size_t)s->dc.rows.ACCF * s->dc.ld;
-    s->theory_moved = true;
-    for (size_t i = 0; i < s->likes.size(); i++) {
-        const auto &e = s->end_theory[i];
-        const auto &l = s->likes[i];
-        const long long n = std::min(e.ld_walker, l.ld_walker);
-        if (same_theory_swap(s, (int)i)) continue;
-        hipLaunchKernelGGL(drag_swap_theory, dim3(16, s->W), dim3(256), 0, stream, flag, 1, s->W, e.dl, e.ld_walker,
-                           const_cast<double *>(l.dl), l.ld_walker, n);
-        HIP_CHECK(hipGetLastError());
-    }
-}
-
-void sampler_step_theory(cmbs *s, int n_steps, cmbs_theory_fn fn, void *user, hipStream_t stream) {
-    if (!s->started) fail(CMBL_ERR_ARG, "cmbs_set_start must be called before cmbs_step_theory");
-    check_theory_fresh(s);
-    if (n_steps <= 0) return;
-    if (s->likes.empty()) {
-        sampler_step(s, n_steps, 0, stream);
-        return;
-    }
-    if (!fn && !s->calc) fail(CMBL_ERR_ARG, "cmbs_step_theory needs a theory function");
-    for (size_t i = 0; i < s->likes.size(); i++) {
-        if (!s->end_theory[i].dl) fail(CMBL_ERR_ARG, "likelihood %zu has no trial-theory buffer", i);
-        if (s->likes[i].ld_walker == 0) fail(CMBL_ERR_ARG, "slow steps need per-walker theory rows");
-    }
-    const double *Ptrial = s->dc.sd + (size_t)s->dc.rows.T * s->dc.ld;
-    auto trial_likes = [&]() {
-        if (!fn) calc_trial_theory(s, Ptrial, stream);
-        else if (fn(user, s->W, Ptrial, (long long)s->dc.ld, stream) != 0)
-            fail(CMBL_ERR_ARG, "theory function failed");
-        eval_likes_drag(s, 1, stream);
-        if (!fn) apply_calc_fail(s, stream);
-    };
-    launch_mh(s, false, true, 0, HistRow{}, stream, 0, s->W);
-    trial_likes();
-    for (int k = 1; k < n_steps; k++) {
-        launch_mh(s, true, true, 0, next_hist(s), stream, 0, s->W);
-        swap_accepted_theory(s, stream);
-        trial_likes();
-    }
-    launch_mh(s, true, false, 0, next_hist(s), stream, 0, s->W);
-    swap_accepted_theory(s, stream);
-}
-
-// After a resume: the theory at every walker's current point (rows P) from the
-// caller's theory function, copied into each likelihood's walker theory rows
-// (the reference recomputes theory at the restart point too,
-// GeneralSetup.f90:123-131).  The restored CurLike and per-likelihood terms are
-// kept as saved, not re-evaluated: theory_fn must reproduce the theory the run
-// had at those points (under a change mask, unchanged likelihoods keep their
-// saved terms).
-__global__ void copy_theory_rows(int W, const double *src, long long src_ld, double *dst, long long dst_ld, long long n)
-{
-    const int w = blockIdx.y;
-    if (w >= W) return;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        dst[(long long)w * dst_ld + i] = src[(long long)w * src_ld + i];
-}
-
-void sampler_refresh_theory(cmbs *s, cmbs_theory_fn fn, void *user, hipStream_t stream) {
-    if (!s->started) fail(CMBL_ERR_ARG, "no chain state: cmbs_set_start or cmbs_load_state first");
-    if (!fn && !s->calc) fail(CMBL_ERR_ARG, "cmbs_refresh_theory needs a theory function");
-    for (size_t i = 0; i < s->likes.size(); i++) {
-        if (!s->end_theory[i].dl) fail(CMBL_ERR_ARG, "likelihood %zu has no trial-theory buffer", i);
-        if (s->likes[i].ld_walker == 0) fail(CMBL_ERR_ARG, "per-walker theory rows needed (ld_walker > 0)");
-    }
-    const double *Pcur = s->dc.sd + (size_t)s->dc.rows.P * s->dc.ld;
-    if (!fn) {   // the calculator: a point outside its box has no theory to resume with
-        calc_trial_theory(s, Pcur, stream);
-        std::vector<int> bad(s->likes.empty() ? 0 : s->W);
-        HIP_CHECK(hipMemcpyAsync(bad.data(), s->calc_fail.p, bad.size() * 4, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        const long n_bad = (long)std::count_if(bad.begin(), bad.end(), [](int b) { return b != 0; });
-        if (n_bad > 0)
-            fail(CMBL_ERR_NUMERIC, "cmbs_refresh_theory: %ld of %d walkers lie outside the theory calculator's box",
-                 n_bad, s->W);
-    } else if (fn(user, s->W, Pcur, (long long)s->dc.ld, stream) != 0) {
-        fail(CMBL_ERR_ARG, "theory function failed");
-    }
-    for (size_t i = 0; i < s->likes.size(); i++) {
-        const auto &e = s->end_theory[i];
-        const auto &l = s->likes[i];
-        hipLaunchKernelGGL(copy_theory_rows, dim3(16, s->W), dim3(256), 0, stream, s->W, e.dl, e.ld_walker,
-                           const_cast<double *>(l.dl), l.ld_walker, std::min(e.ld_walker, l.ld_walker));
-        HIP_CHECK(hipGetLastError());
-    }
-    s->theory_stale = false;
-}
+#include "slowstep.h"
 
 void sampler_set_groups(cmbs *s, int n_groups) {
     {   // the groups step together: a common known loop index carries over to the new split

@@ -1245,6 +1245,134 @@ def test_dragging_fused_plik_lensing_at_bounds(cmbl_golden, refdata, tmp_path):
         assert lk[w] == pytest.approx(ref, rel=1e-12)
 
 
+_FUSED_SLOW_ORACLES = {}
+
+
+def _fused_slow_sampler(cmbl_golden, refdata, path, n_trial=1, shared_row=False):
+    """test_dragging_fused_plik_lensing's problem (synthetic plik_lite 12345 +
+    lensing_consext8 on one walker theory buffer, A slow, calPlanck fast, its
+    seeds, covariance and bounds; W = 130: two 64-walker tiles and a remainder
+    of 2) with one trial-theory buffer for both likelihoods (n_trial 1) or one
+    each (2).  shared_row: every walker reads one theory row (ld_walker 0).
+    Returns the sampler, the walker theory, base and a theory function that
+    fills every trial buffer with A_w x base."""
+    import os
+
+    from cosmomc_amd import _native as N
+    from cosmomc_amd.likelihood import NativeCMBLikelihood
+    from cosmomc_amd.sampler import BatchedMCMC
+    c = cmbl_golden["cases"]["lensing_consext8"]
+    data = syn.make_plik_lite(12345)
+    plik = NativeCMBLikelihood("PLIK_LITE", data.write(str(path)))
+    lens = NativeCMBLikelihood(c["tag"], os.path.join(refdata, c["dataset"]), c["overrides"])
+    plik.nuisance_indices = [2]
+    lens.nuisance_indices = [2]
+    W = 130
+    base = torch.tensor(syn.walker_theory(1, seed=4, n_fields=10, ld_field=2512), device="cuda")[0]
+    theory = base.unsqueeze(0).expand(W, -1, -1) if shared_row else base.unsqueeze(0).repeat(W, 1, 1).contiguous()
+    trials = [torch.empty((W,) + tuple(base.shape), dtype=base.dtype, device="cuda") for _ in range(n_trial)]
+    pmin, pmax = np.array([0.95, 0.9]), np.array([1.05, 1.1])
+    pm, ps = np.array([0.0, 1.0]), np.array([0.0, 0.0025])
+    s = BatchedMCMC(W, 2, [1, 2], [[1], [2]], 1, pmin, pmax, pm, ps, propose_scale=2.4, seed_ij=93, seed_kl=94)
+    s.set_covariance(np.diag([0.002 ** 2, 0.0025 ** 2]))
+    s.add_likelihood(plik, theory)
+    s.add_likelihood(lens, theory)
+    assert N.lib().cmamd_debug_fused(s._h) > 0
+    s.set_trial_theory(0, trials[0])
+    s.set_trial_theory(1, trials[-1])
+    s.set_start(np.tile([1.0, 1.0], (W, 1)))
+    s.enable_history(64)
+
+    def theory_fn(P_trial):
+        for t in trials:
+            torch.mul(base.unsqueeze(0), P_trial[0].reshape(-1, 1, 1), out=t)
+        if n_trial == 2:
+            # plik_lite reads TT, TE and EE only: a pass that took its buffer for the lensing
+            # likelihood as well would give NaN terms (the lensing buffer, swapped last, is whole)
+            trials[0][:, 3:] = float("nan")
+    return s, theory, base, theory_fn
+
+
+def _assert_fused_slow_oracles(cmbl_golden, refdata, s, theory, base, what):
+    """test_dragging_fused_plik_lensing's assertions after the last step, at its
+    tolerances: some slow move accepted, walkers 0, 64 and W - 1 carry
+    P[w, 0] x base, their last terms are the oracles' there and CurLike is
+    terms + prior."""
+    import os
+
+    import cmblikes_oracle as co
+    c = cmbl_golden["cases"]["lensing_consext8"]
+    if not _FUSED_SLOW_ORACLES:
+        _FUSED_SLOW_ORACLES["plik"] = po.PlikLite(syn.make_plik_lite(12345))
+        _FUSED_SLOW_ORACLES["lens"] = co.CMBLikesOracle(os.path.join(refdata, c["dataset"]), c["overrides"], c["tag"])
+    op, ol = _FUSED_SLOW_ORACLES["plik"], _FUSED_SLOW_ORACLES["lens"]
+    P, lk, mult, nacc = s.state()
+    terms = s.history_terms(s.history_count() - 1, 1)[0]
+    assert np.any(np.abs(P[:, 0] - 1.0) > 1e-6), f"{what}: no slow move was accepted"
+    th, b = theory.cpu().numpy(), base.cpu().numpy()
+    for w in (0, 64, s.W - 1):
+        np.testing.assert_allclose(th[w], P[w, 0] * b, rtol=1e-15, atol=0, err_msg=what)
+        assert terms[0, w] == pytest.approx(op.loglike(th[w, :3], P[w, 1]), rel=1e-9), what
+        assert terms[1, w] == pytest.approx(ol.loglike(th[w], P[w, 1:2]), rel=1e-10), what
+        ref = terms[0, w] + terms[1, w] + 0.5 * ((P[w, 1] - 1.0) / 0.0025) ** 2
+        assert lk[w] == pytest.approx(ref, rel=1e-12), what
+
+
+def test_step_theory_fused_pair_shared_trial_buffer(cmbl_golden, refdata, tmp_path):
+    """cmbs_step_theory on the fused pair with one trial-theory buffer (the
+    window pass runs on the trial theories): 12 steps in one call and as 12
+    calls of one step give the same history, terms, state and theory rows bit
+    for bit, and the oracle assertions of test_dragging_fused_plik_lensing
+    hold."""
+    out = []
+    for tag, calls in (("one", (12,)), ("each", (1,) * 12)):
+        s, theory, base, fn = _fused_slow_sampler(cmbl_golden, refdata, tmp_path / tag)
+        for n in calls:
+            s.step_theory(n, theory_fn=fn)
+        n = s.history_count()
+        assert n == 12
+        out.append((s.history_host(0, n), s.history_terms(0, n), *s.state(), theory.cpu().numpy()))
+        if tag == "one":
+            _assert_fused_slow_oracles(cmbl_golden, refdata, s, theory, base, "step_theory(12)")
+        s.close()
+    for x, y in zip(*out):
+        assert np.array_equal(x, y)
+
+
+@pytest.mark.parametrize("entry", ["step_theory", "step_drag"])
+def test_fused_pair_distinct_trial_buffers(cmbl_golden, refdata, tmp_path, entry):
+    """The fused pair with a trial-theory buffer per likelihood, both filled by
+    the theory function: the trial (end) set cannot run as one pass, so each
+    likelihood evaluates its own buffer there -- in step_drag the paired
+    interpolation launches (cmamd_debug_drag_pair at its default) are refused
+    and the start set still runs fused.  Same oracle assertions; plik_lite's
+    buffer is NaN in the fields only the lensing likelihood reads, so one pass
+    over it for both would show.  (No bit equality with the shared-buffer run:
+    the pass and a likelihood's own evaluation split the window sums
+    differently)"""
+    s, theory, base, fn = _fused_slow_sampler(cmbl_golden, refdata, tmp_path, n_trial=2)
+    getattr(s, entry)(12, theory_fn=fn)
+    assert s.history_count() == 12
+    _assert_fused_slow_oracles(cmbl_golden, refdata, s, theory, base, f"{entry}(12), two trial buffers")
+    s.close()
+
+
+def test_step_drag_refuses_shared_theory_row_before_any_launch(cmbl_golden, refdata, tmp_path):
+    """cmbs_step_drag with data likelihoods on one theory row shared by every
+    walker (ld_walker 0: an accepted drag has no row of its own to keep its
+    theory in) fails with CMBL_ERR_ARG before anything is launched: the state
+    image and the history count are what they were."""
+    from cosmomc_amd._native import NativeError
+    s, theory, base, fn = _fused_slow_sampler(cmbl_golden, refdata, tmp_path, shared_row=True)
+    before, n0 = s.save_state(), s.history_count()
+    with pytest.raises(NativeError) as e:
+        s.step_drag(12, theory_fn=fn)
+    assert e.value.code == -1
+    assert s.history_count() == n0
+    assert s.save_state() == before
+    s.close()
+
+
 @pytest.mark.parametrize("W", [130, 1024])
 def test_drag_staged_matches_hbm(cmbl_golden, refdata, tmp_path, W):
     """The drag stages on an LDS image of the walkers' state (drag_staged_kernel,

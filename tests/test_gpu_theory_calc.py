@@ -486,6 +486,34 @@ def test_no_calculator_and_no_callback_still_refused(tmp_path):
     calc.close()
 
 
+def test_callback_steps_ignore_the_calculators_flags(tmp_path):
+    """A theory function passed to step_theory / step_drag is the theory
+    source even when a calculator is set, and the out-of-box flags of the
+    calculator's last call stay out of its steps: after a refresh_theory(None)
+    that flagged every walker (box A in [1.2, 1.3]; code -4, rows untouched),
+    callback steps give the bits of a run that never had a calculator."""
+    from cosmomc_amd._native import NativeError
+    outs = []
+    for tag in ("plain", "flagged"):
+        r = _Run(tmp_path, tag, FULL_W, "callback", WIDE, None, 1, 1.0, FULL_SEEDS, FULL_COV, 8, cal_bounds=WIDE)
+        r.start()
+        off = None
+        if tag == "flagged":
+            off = _one_term(r.bh, (1.2, 1.3))
+            r.s.set_theory_calculator(off)
+            with pytest.raises(NativeError) as e:
+                r.s.refresh_theory(None)
+            assert e.value.code == -4, e.value
+        r.s.step_theory(4, theory_fn=r.fn)
+        r.s.step_drag(2, theory_fn=r.fn)
+        outs.append(r.outputs())
+        r.close()
+        if off is not None:
+            off.close()
+    assert np.any(outs[0][2][:, 0] != 1.0), "no slow move was accepted"
+    _assert_same(outs[0], outs[1], "calculator set and flagged")
+
+
 @pytest.mark.parametrize("share_trial", [False, True])
 def test_two_trial_buffers(tmp_path, share_trial):
     """Two likelihood handles on the same dataset with theory buffers of their
