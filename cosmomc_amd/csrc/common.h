@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <map>
 #include <memory>
@@ -69,6 +70,21 @@ struct DevBuf {
     template <class T> T *as() const { return static_cast<T *>(p); }
     void upload(const void *src, size_t n) { HIP_CHECK(hipMemcpy(p, src, n, hipMemcpyHostToDevice)); }
 };
+
+// A host table on the device: d is reallocated to hold v (16 bytes when v is
+// empty, so the returned address is never null) and filled with it.
+template <class T> inline T *upload(DevBuf &d, const std::vector<T> &v) {
+    const size_t bytes = v.size() * sizeof(T);
+    d.alloc(std::max<size_t>(bytes, 16));
+    if (bytes) d.upload(v.data(), bytes);
+    return d.as<T>();
+}
+
+// 16-byte (double2) loads of theory rows dl[w * ld_walker + f * ld_field + l]
+// at even l need aligned rows; a caller adds what its own l ranges require.
+inline bool theory_vec16(const double *dl, long long ld_field, long long ld_walker) {
+    return (reinterpret_cast<uintptr_t>(dl) & 15) == 0 && ld_field % 2 == 0 && ld_walker % 2 == 0;
+}
 
 // ---------------- per-kernel event timing (cmbl_profile_*) ----------------
 // Off by default.  When on, every library kernel launch is bracketed by a
@@ -153,6 +169,9 @@ std::string dirname_of(const std::string &path);
 bool file_exists(const std::string &path);
 // File%LoadTxt: whitespace-separated numeric matrix, '#' comment lines skipped
 std::vector<std::vector<double>> load_txt(const std::string &path);
+// a Fortran real ("1.5D-3") as C reads it ("1.5e-3"), and its value (std::stod: throws on no number)
+std::string fortran_real(std::string s);
+double parse_fortran_double(const std::string &s);
 std::vector<std::string> split_ws(const std::string &s);
 // .paramnames file -> space-separated names (derived '*' stripped), count
 std::string load_paramnames(const std::string &path, int *count, std::string *derived = nullptr,
@@ -251,6 +270,12 @@ struct Like {
         if (W <= 0 || n_derived <= 0) return;
         if (!out || ld_out < n_derived) fail(CMBL_ERR_ARG, "derived output needs %d columns", n_derived);
         HIP_CHECK(hipMemset2DAsync(out, (size_t)ld_out * 8, 0, (size_t)n_derived * 8, W, stream));
+    }
+    // The nuisance rows to hand to the kernels: nuis, which a likelihood with
+    // parameters needs; one without never reads them, so any address (unread) serves.
+    const double *nuisance_rows(const double *nuis, const void *unread) const {
+        if (n_nuis > 0 && !nuis) fail(CMBL_ERR_ARG, "%s needs its %d nuisance parameters", name.c_str(), n_nuis);
+        return nuis ? nuis : static_cast<const double *>(unread);
     }
     int speed = -1;
     int cl_lmax[16] = {0};

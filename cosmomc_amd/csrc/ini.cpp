@@ -149,4 +149,12 @@ std::vector<std::vector<double>> load_txt(const std::string &path) {
     return rows;
 }
 
+std::string fortran_real(std::string s) {
+    for (auto &ch : s)
+        if (ch == 'd' || ch == 'D') ch = 'e';
+    return s;
+}
+
+double parse_fortran_double(const std::string &s) { return std::stod(fortran_real(s)); }
+
 }  // namespace cmamd

@@ -270,12 +270,9 @@ struct PlikLite final : Like {
         int wmax = lmax_needed;
         for (int f = 0; f < 3; f++) wmax = std::max(wmax, fr.hi[f]);
         wts.resize((size_t)wmax + 2, 0.0);
-        d_wts.alloc(wts.size() * 8);
-        d_wts.upload(wts.data(), wts.size() * 8);
-        d_bins.alloc(binfo.size() * sizeof(BinInfo));
-        d_bins.upload(binfo.data(), binfo.size() * sizeof(BinInfo));
-        d_X.alloc(Xp.size() * 8);
-        d_X.upload(Xp.data(), Xp.size() * 8);
+        upload(d_wts, wts);
+        upload(d_bins, binfo);
+        upload(d_X, Xp);
         const size_t lds = (size_t)lds_doubles * 8;
         if (lds > 64 * 1024)
             HIP_CHECK(hipFuncSetAttribute((const void *)plik_bin_delta,
@@ -310,7 +307,7 @@ struct PlikLite final : Like {
         a.Np = Np;
         a.fr = fr;
         // 16-byte D_l loads need 16-byte aligned rows and the widened ranges inside each row
-        a.vec_ok = ((reinterpret_cast<uintptr_t>(dl) & 15) == 0) && (ld_field % 2 == 0) && (ld_walker % 2 == 0);
+        a.vec_ok = theory_vec16(dl, ld_field, ld_walker);
         for (int f = 0; f < 3; f++)
             if (fr.hi[f] >= fr.lo[f] && fr.hi[f] >= ld_field) a.vec_ok = 0;
         a.lds_doubles = lds_doubles;

@@ -254,14 +254,12 @@ void QuadForm::init(const std::vector<double> &M, int n_) {
             const double v = M[(size_t)i * n + j];
             ct[(size_t)i * Np + j] = (i / QF_TILE == j / QF_TILE) ? 0.5 * v : v;
         }
-    d_ct.alloc(ct.size() * 8);
-    d_ct.upload(ct.data(), ct.size() * 8);
+    upload(d_ct, ct);
     for (int kb = 1; kb <= MAXKB; kb++) {
         items[kb].clear();
         for (int I = 0; I < nblk; I++)
             for (int J0 = I; J0 < nblk; J0 += kb) items[kb].push_back(QFItem{I, J0, std::min(kb, nblk - J0), 0});
-        d_items[kb].alloc(items[kb].size() * sizeof(QFItem));
-        d_items[kb].upload(items[kb].data(), items[kb].size() * sizeof(QFItem));
+        upload(d_items[kb], items[kb]);
     }
     kb_for_tiles.clear();
 }

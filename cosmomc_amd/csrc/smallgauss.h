@@ -1,7 +1,7 @@
 // Small gaussian CMBlikes chi^2 (nX <= 64 bandpowers, e.g. Planck lensing 9,
 // SPT-SZ 47): binned spectra, bigX = C - Chat and chi^2 = bigX^T C^-1 bigX in
 // one workgroup body (CMBlikes.f90:1183-1225; Matrix_QuadForm as row sums
-// y = M x, then x.y).  Shared by cmbl_gauss_small_kernel (cmblikes.hip) and by
+// y = M x, then x.y).  Shared by cmbl_gauss_small_kernel (cmblreduce.h) and by
 // the deferred quadratic form's launch (quadform.hip, quadform_corun), where
 // its workgroups run beside the quadratic form's instead of in a launch of
 // their own.  The arguments are SmallGaussLaunch (common.h).

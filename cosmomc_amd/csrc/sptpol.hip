@@ -321,11 +321,8 @@ std::vector<std::string> read_lines(const std::string &path) {
 }
 
 double num(const std::string &tok) {
-    std::string t = tok;
-    for (auto &ch : t)
-        if (ch == 'd' || ch == 'D') ch = 'e';
     try {
-        return std::stod(t);
+        return parse_fortran_double(tok);
     } catch (...) {
         fail(CMBL_ERR_FORMAT, "SPTpol: bad number '%s'", tok.c_str());
     }
@@ -353,9 +350,7 @@ bool logical(const Ini &ini, const std::string &key) {   // Ini%Read_Logical(key
 double real4(const Ini &ini, const std::string &key, float def) {   // Ini%Read_Real: a REAL(4)
     std::string v = ini.str(key);
     if (v.empty()) return (double)def;
-    for (auto &ch : v)
-        if (ch == 'd' || ch == 'D') ch = 'e';
-    return (double)std::strtof(v.c_str(), nullptr);
+    return (double)std::strtof(fortran_real(v).c_str(), nullptr);
 }
 
 std::string required_path(const Ini &ini, const std::string &key) {   // Read_String_Default(key, '')
@@ -503,36 +498,22 @@ struct SPTpol final : Like {
         }
         if (rows.empty()) rows.push_back(0);
         need_lmax = lmax + 1;     // dls(1:lmax+1) (ClArray into dimension(spt_windows_lmax+1))
-        d_items.alloc(std::max<size_t>(1, items.size()) * sizeof(SPItem));
-        if (!items.empty()) d_items.upload(items.data(), items.size() * sizeof(SPItem));
-        d_wts.alloc(std::max<size_t>(1, wts.size()) * 8);
-        if (!wts.empty()) d_wts.upload(wts.data(), wts.size() * 8);
-        d_tabs.alloc(std::max<size_t>(1, tabs.size()) * 8);
-        if (!tabs.empty()) d_tabs.upload(tabs.data(), tabs.size() * 8);
-        d_rowoff.alloc(roff.size() * 4);
-        d_rowoff.upload(roff.data(), roff.size() * 4);
-        d_rows.alloc(rows.size() * 4);
-        d_rows.upload(rows.data(), rows.size() * 4);
-        d_beam.alloc(std::max<size_t>(1, beam.size()) * 8);
-        if (!beam.empty()) d_beam.upload(beam.data(), beam.size() * 8);
-        d_spec.alloc(spec.size() * 8);
-        d_spec.upload(spec.data(), spec.size() * 8);
         dev.nitem = (int)items.size();
         dev.lmin = lmin;
         dev.lmax = lmax;
-        dev.items = d_items.as<SPItem>();
-        dev.wts = d_wts.as<double>();
-        dev.tabs = d_tabs.as<double>();
+        dev.items = upload(d_items, items);
+        dev.wts = upload(d_wts, wts);
+        dev.tabs = upload(d_tabs, tabs);
         for (int k = 0; k < 3; k++) dev.field[k] = fields[k];
         dev.nall = nall;
         dev.nbin = nbin;
         dev.nband = nband;
         dev.Np = qf.Np;
         dev.nbeam = nbeam;
-        dev.row_off = d_rowoff.as<int>();
-        dev.rows = d_rows.as<int>();
-        dev.beam_err = d_beam.as<double>();
-        dev.spec = d_spec.as<double>();
+        dev.row_off = upload(d_rowoff, roff);
+        dev.rows = upload(d_rows, rows);
+        dev.beam_err = upload(d_beam, beam);
+        dev.spec = upload(d_spec, spec);
     }
 
     void read_teee(const Ini &ini) {           // SPTpol_TEEE_ReadIni / InitSPTpolData (:56-352)
@@ -766,7 +747,7 @@ struct SPTpol final : Like {
     void loglike_batch(int W, const double *dl, long long ld_field, long long ld_walker, const double *nuis,
                        long long ld_nuis, double *out, void *ws, hipStream_t stream) override {
         if (W <= 0) return;
-        if (!nuis) fail(CMBL_ERR_ARG, "%s needs its %d nuisance parameters", name.c_str(), n_nuis);
+        nuis = nuisance_rows(nuis, nullptr);   // (n_nuis >= 11: read_teee / read_bb)
         if (ld_nuis < n_nuis && W > 1) fail(CMBL_ERR_ARG, "ld_nuis %lld < %d nuisance parameters", ld_nuis, n_nuis);
         if (ld_field < need_lmax + 1) fail(CMBL_ERR_ARG, "ld_field %lld < %d (l up to %d)", ld_field, need_lmax + 1, need_lmax);
         const int maxf = kind == SP_BB ? 5 : 2;
@@ -781,7 +762,7 @@ struct SPTpol final : Like {
         double *partial = reinterpret_cast<double *>(base + o.part);
         double *addend = reinterpret_cast<double *>(base + o.add);
         const int tiles = (W + 63) / 64;
-        const bool vec_ok = ((reinterpret_cast<uintptr_t>(dl) & 15) == 0) && ld_field % 2 == 0 && ld_walker % 2 == 0;
+        const bool vec_ok = theory_vec16(dl, ld_field, ld_walker);
         if (dev.nitem > 0) {
             const int nblk = 8 * tiles * ((dev.nitem + 7) / 8);
             timed_launch("sptpol_window_kernel", stream, [&](hipEvent_t e0, hipEvent_t e1) {

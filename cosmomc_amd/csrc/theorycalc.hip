@@ -208,16 +208,11 @@ void theorycalc_create(cmbt *t, const cmbt_config_t *c) {
     t->lmax = c->lmax;
     t->Lp = Lp;
     t->pidx.assign(c->param_index, c->param_index + n_in);
-    t->meta.alloc(meta.size() * 8);
-    t->meta.upload(meta.data(), meta.size() * 8);
-    t->pidx_d.alloc((size_t)n_in * 4);
-    t->pidx_d.upload(t->pidx.data(), (size_t)n_in * 4);
-    t->fields_d.alloc((size_t)nf * 4);
-    t->fields_d.upload(c->fields, (size_t)nf * 4);
-    t->expo.alloc((size_t)Kp * 8);
-    t->expo.upload(expo.data(), (size_t)Kp * 8);
-    t->coef.alloc(coef.size() * 8);
-    t->coef.upload(coef.data(), coef.size() * 8);
+    upload(t->meta, meta);
+    upload(t->pidx_d, t->pidx);
+    upload(t->fields_d, std::vector<int>(c->fields, c->fields + nf));
+    upload(t->expo, expo);
+    upload(t->coef, coef);
     HIP_CHECK(hipFuncSetAttribute((const void *)theory_calc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)tc_lds_bytes(TC_MAXTERMS)));
 }

@@ -3,7 +3,7 @@
 // A work item is an l range of one theory field with up to 64 columns from
 // any of the stages (four 16-column MFMA blocks); a workgroup takes one item
 // for 64 walkers and walks the range in 32-l steps.  The contraction is
-// cmbl_window_direct's (cmblikes.hip): lane (walker li, quarter kq) holds the 8
+// cmbl_window_direct's (cmblwindow.h): lane (walker li, quarter kq) holds the 8
 // l {l0 + 32 st + 8 j + 2 kq + h : j < 4, h < 2} of its walker's row in slot
 // 2 j + h (16-byte loads, two steps ahead of the MFMAs), and MFMA step
 // s = 2 j + h contracts the four l {8 j + 2 kq + h} against the weights, which
@@ -415,16 +415,12 @@ bool TheoryPass::build(const std::vector<WinStage> &stages) {
     }
     items = its;
     nstage = (int)stages.size();
-    auto up = [](DevBuf &d, const void *p, size_t bytes) {
-        d.alloc(std::max<size_t>(16, bytes));
-        if (bytes) d.upload(p, bytes);
-    };
-    up(d_items, items.data(), items.size() * sizeof(TPItem));
-    up(d_cols, cols.data(), cols.size() * sizeof(TPCol));
+    upload(d_items, items);
+    upload(d_cols, cols);
     w.resize(w.size() + 4 * 16 * TP_CHUNK, 0.0);   // theory_window_vec reads four blocks of every item
-    up(d_w, w.data(), w.size() * 8);
-    up(d_emit, emit.data(), emit.size() * sizeof(unsigned long long));
-    up(d_cmap, cmap.data(), cmap.size());
+    upload(d_w, w);
+    upload(d_emit, emit);
+    upload(d_cmap, cmap);
     return true;
 }
 
@@ -482,8 +478,7 @@ void TheoryPass::plan_units(int tiles) {
             for (size_t r = 0; r < cu[x][k].size(); r++) table[((size_t)r * cpx + k) * NX + x] = cu[x][k][r];
     nblk = (int)table.size();
     per_round = NX * cpx;
-    d_units.alloc(table.size() * sizeof(int2));
-    d_units.upload(table.data(), table.size() * sizeof(int2));
+    upload(d_units, table);
     unit_tiles = tiles;
 }
 
@@ -502,7 +497,7 @@ void TheoryPass::launch_pair(const double *dla, long long lfa, long long lwa, co
 
 bool TheoryPass::vec_ok(const double *dl, long long ld_field, long long ld_walker) const {
     // (four blocks would not fit the registers: theory_window_kernel<4>)
-    return ((reinterpret_cast<uintptr_t>(dl) & 15) == 0) && ld_field % 2 == 0 && ld_walker % 2 == 0 && max_nsb <= 2;
+    return theory_vec16(dl, ld_field, ld_walker) && max_nsb <= 2;
 }
 
 TPDev TheoryPass::dev_args(const TPOut *outs, int W) {
@@ -525,7 +520,7 @@ void TheoryPass::launch(const double *dl, long long ld_field, long long ld_walke
                         hipStream_t stream) {
     if (W <= 0 || items.empty()) return;
     const TPDev c = dev_args(outs, W);
-    const int vec_ok = ((reinterpret_cast<uintptr_t>(dl) & 15) == 0) && ld_field % 2 == 0 && ld_walker % 2 == 0;
+    const int vec_ok = theory_vec16(dl, ld_field, ld_walker);
     const int tiles = (W + 63) / 64;
     if (this->vec_ok(dl, ld_field, ld_walker)) {
         timed_launch("theory_window_kernel", stream, [&](hipEvent_t e0, hipEvent_t e1) {

@@ -154,7 +154,7 @@ def test_hl_non_positive_definite_theory_is_nan(cmbl_golden, refdata, case):
 @pytest.mark.parametrize("case", ["bkplanck_all_maps", "bk15_B_12maps"])
 def test_hl_result_independent_of_walker_order(cmbl_golden, refdata, case):
     """A walker's HL -lnL depends on its own theory and nuisances only: the
-    Jacobi sweep stop is per problem (cmblikes.hip hl_ojacobi), so which
+    Jacobi sweep stop is per problem (cmblhl.h hl_ojacobi), so which
     walkers share its wave does not change its bits.  The same 192 walkers in
     their order, reversed, and in a random permutation give the same values
     bit for bit, against one another and against each walker evaluated alone."""
