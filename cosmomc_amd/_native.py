@@ -52,6 +52,11 @@ class CmbtConfig(C.Structure):
                 ("coef", C.POINTER(C.c_double))]
 
 
+class CmbtDerivedConfig(C.Structure):
+    _fields_ = [("n_derived", C.c_int), ("coef", C.POINTER(C.c_double)),
+                ("lo", C.POINTER(C.c_double)), ("hi", C.POINTER(C.c_double))]
+
+
 _lib = None
 
 # cmbs_theory_fn: int (*)(void *user, int W, const double *P_end, long long ld, void *stream)
@@ -121,6 +126,9 @@ def lib():
         L.cmbt_last_error.argtypes = [vp]
         L.cmbt_last_error.restype = C.c_char_p
         L.cmbt_eval.argtypes = [vp, i, vp, ll, i, vp, ll, ll, vp, vp]
+        L.cmbt_set_derived.argtypes = [vp, C.POINTER(CmbtDerivedConfig)]
+        L.cmbt_derived_count.argtypes = [vp]
+        L.cmbt_derived_eval.argtypes = [vp, i, vp, ll, i, vp, ll, vp, vp]
         L.cmbs_set_theory_calculator.argtypes = [vp, vp]
         L.cmbs_collector_enable.argtypes = [vp, i]
         L.cmbs_collector_add.argtypes = [vp, vp, i, i, i, vp]

@@ -32,9 +32,17 @@ at the point (``cmbs_history_terms_host``), ``chi2_prior`` = 2 x (like -
 sum of terms), and ``chi2_<type>`` sums for every likelihood type used more
 than once; ``root.likelihoods`` lists them (OutputDescription, :792-812).
 With ``derived`` given, the likelihoods' own derived parameters (the '*'
-names of their nuisance .paramnames, e.g. SMICA's D_l(2000)) come first among
-the derived columns, as in addLikelihoodDerivedParams (:772-777):
+names of their nuisance .paramnames, e.g. SMICA's D_l(2000)) come before the
+chi2 columns, as in addLikelihoodDerivedParams (:772-777):
 ``LikelihoodDerived`` evaluates them on the device for every history row.
+With ``theory_derived`` given, the parameterization's derived parameters (H0,
+omegam, sigma8, ..., DL40 .. DL2000: CosmologyParameterizations.f90:189-272,
+written by calclike.f90:447-448) come first among the derived columns: a
+likelihood's derived_indices are offsets into the whole derived list, behind
+the parameterization's (GeneralTypes.f90:661).  ``TheoryDerived`` evaluates
+them from the theory calculator's derived surfaces.  Column order of rows and
+of ``root.paramnames``: used parameters, theory-derived, likelihood-derived,
+chi2_*.
 """
 from __future__ import annotations
 
@@ -71,12 +79,13 @@ class ChainWriter:
     ranges: list of (min, max) or None."""
 
     def __init__(self, root: str, names, labels=None, ranges=None, walkers=None, first_chain: int = 1,
-                 likelihoods=None, burn_in: int = 2, thin: int = 1, derived=None):
+                 likelihoods=None, burn_in: int = 2, thin: int = 1, derived=None, theory_derived=None):
         """likelihoods: one (tag, type, name, version) per sampler likelihood,
         in add_likelihood order, to add the chi2_* columns.  burn_in / thin as
         TChainSampler%burn_in and MoveDone's thin_fac (module docstring).
         derived: a LikelihoodDerived (its names, and the columns it computes
-        from the history's points)."""
+        from the history's points).  theory_derived: a TheoryDerived (names,
+        hard ranges and columns of the calculator-derived parameters)."""
         self.root = root
         self.names = list(names)
         self.labels = list(labels) if labels is not None else list(names)
@@ -85,6 +94,7 @@ class ChainWriter:
         self.first_chain = first_chain
         self.likelihoods = [tuple(x) for x in likelihoods] if likelihoods else []
         self.like_derived = derived
+        self.theory_derived = theory_derived
         self.pending = {}                          # walker -> [point values (like, P..., chi2...), count]
         self.next_step = None
         self.burn_in, self.thin = int(burn_in), max(1, int(thin))
@@ -98,6 +108,8 @@ class ChainWriter:
         with open(root + ".paramnames", "w") as f:
             for n, lab in zip(self.names, self.labels):
                 f.write(f"{n}\t{lab}\n")
+            for n, lab in (self.theory_derived.names if self.theory_derived else []):
+                f.write(f"{n}*\t{lab}\n")
             for n, lab in (self.like_derived.names if self.like_derived else []):
                 f.write(f"{n}*\t{lab}\n")
             for n, lab in derived:
@@ -106,6 +118,9 @@ class ChainWriter:
             with open(root + ".ranges", "w") as f:
                 for n, r in zip(self.names, ranges):
                     f.write(f"{n}\t{r[0]!r}\t{r[1]!r}\n")
+                for n, mn, mx in (self.theory_derived.ranges if self.theory_derived else []):
+                    lim = "".join(f"{'    N' if v is None else fortran_e(v):<17}" for v in (mn, mx))
+                    f.write(f"{n:<22}{lim}\n")         # AddDerivedRange's (1A22,1A17,1A17), a missing side '    N'
                 for n, _ in derived:                 # AddDerivedRange(name, mn=0) (ObjectParamNames.f90:480-508)
                     f.write(f"{n:<22}{fortran_e(0.0)}{'    N':<17}\n")
         if self.likelihoods:
@@ -169,7 +184,8 @@ class ChainWriter:
         if self.likelihoods and (terms is None or np.shape(terms)[1] != len(self.likelihoods)):
             raise ValueError("chi2 columns need the per-likelihood history terms of every likelihood")
         walkers = range(W) if self.walkers is None else self.walkers
-        dcols = self.like_derived.columns(rows[:, :n1 - 1, :]) if self.like_derived else None   # [steps, nd, W]
+        dcols = [d.columns(rows[:, :n1 - 1, :]) for d in (self.theory_derived, self.like_derived) if d]
+        dcols = np.concatenate(dcols, axis=1) if dcols else None
         for w in walkers:
             pts = np.concatenate([rows[:, n1 - 1:n1, w], rows[:, :n1 - 1, w]], axis=1)   # like, P...
             if dcols is not None:
@@ -284,3 +300,30 @@ class LikelihoodDerived:
             for k, ix in enumerate(l.derived_indices):
                 out[:, ix - 1] = d[:, k]
         return out.reshape(steps, W, self.n).transpose(0, 2, 1)
+
+
+class TheoryDerived:
+    """The theory calculator's derived parameters for chain rows (the
+    parameterization's CalcDerivedParams, CosmologyParameterizations.f90:189-272),
+    evaluated on the device through ``calc.derived``.
+
+    calc: a PolynomialTheory after set_derived; params_used: the 1-based
+    parameter indices of the history rows; P_fixed: the full parameter vector
+    supplying the values of parameters that are not used (fixed)."""
+
+    def __init__(self, calc, params_used, P_fixed):
+        self.calc = calc
+        self.params_used = [int(i) for i in params_used]
+        self.P_fixed = np.asarray(P_fixed, dtype=np.float64)
+        self.names = list(calc.derived_names)
+        self.ranges = [r for r in calc.derived_ranges if r[1] is not None or r[2] is not None]
+
+    def columns(self, P_used):
+        """P_used [steps, n_used, W] -> derived [steps, n_derived, W], one
+        cmbt_derived_eval over all steps x W points."""
+        steps, nu, W = P_used.shape
+        full = np.broadcast_to(self.P_fixed, (steps, W, self.P_fixed.size)).copy()
+        for k, i in enumerate(self.params_used):
+            full[:, :, i - 1] = P_used[:, k, :]
+        d = self.calc.derived(full.reshape(steps * W, -1)).cpu().numpy()      # [n_derived, steps * W]
+        return d.reshape(d.shape[0], steps, W).transpose(1, 0, 2)

@@ -403,6 +403,21 @@ int cmbt_eval(cmbt_t *t, int W, const double *P, long long ld, int num_params, d
     });
 }
 
+int cmbt_set_derived(cmbt_t *t, const cmbt_derived_config_t *cfg) {
+    if (!t) return CMBL_ERR_ARG;
+    return guarded(&t->last_error, [&] { cmamd::theorycalc_set_derived(t, cfg); });
+}
+
+int cmbt_derived_count(const cmbt_t *t) { return t ? t->n_derived : 0; }
+
+int cmbt_derived_eval(cmbt_t *t, int M, const double *P, long long ld, int num_params, double *out, long long ld_out,
+                      int *fail, void *stream) {
+    if (!t) return CMBL_ERR_ARG;
+    return guarded(&t->last_error, [&] {
+        cmamd::theorycalc_derived_eval(t, M, P, ld, num_params, out, ld_out, fail, (hipStream_t)stream);
+    });
+}
+
 int cmbs_set_theory_calculator(cmbs_t *s, cmbt_t *calc) {
     if (!s) return CMBL_ERR_ARG;
     return guarded(&s->last_error, [&] { cmamd::sampler_set_theory_calculator(s, calc); });

@@ -3,7 +3,9 @@
 // the place of the reference's calculator object in its emulator form
 // (Calculator_PICO.f90: a polynomial fit of the C_l; a point outside the
 // training box gives error = 1, which TheoryLike_GetLogLikeMain turns into
-// logZero, calclike.f90:308-313).
+// logZero, calclike.f90:308-313).  Its derived outputs are the
+// parameterization's derived parameters and, with ranges, the hard cuts of
+// TP_NonBaseParameterPriors (CosmologyParameterizations.f90:90-112, 189-272).
 #pragma once
 
 #include <string>
@@ -16,6 +18,9 @@ namespace cmamd {
 // per workgroup, the coefficient table staged through LDS TC_KC terms at a time
 constexpr int TC_TW = 32, TC_TN = 256, TC_KC = 8, TC_THREADS = 256;
 constexpr int TC_MAXIN = 16, TC_MAXTERMS = 256, TC_MAXORDER = 4;
+// theory_derived_kernel's tile: a point per thread, all its (up to TD_ND)
+// scalar outputs in the thread's registers
+constexpr int TD_TM = 256, TD_ND = CMBT_MAXDERIVED, TD_THREADS = 256;
 }  // namespace cmamd
 
 struct cmbt {
@@ -26,10 +31,20 @@ struct cmbt {
     // fields [n_fields], expo [Kp] (4 bits per input), coef [n_fields][Kp][Lp]
     // (terms padded to TC_KC and l to TC_TN with zeros)
     cmamd::DevBuf meta, pidx_d, fields_d, expo, coef;
+    // derived outputs (cmbt_set_derived; n_derived == 0: none): dcoef
+    // [Kp][TD_ND] (terms and outputs padded with zeros), dlim [2][TD_ND] (lo
+    // then hi, -inf / +inf where there is no limit); ranged: a lo or hi table
+    // was given, so the failure flags include the range test
+    int n_derived = 0;
+    bool ranged = false;
+    cmamd::DevBuf dcoef, dlim;
 };
 
 namespace cmamd {
 void theorycalc_create(cmbt *t, const cmbt_config_t *cfg);
 void theorycalc_eval(cmbt *t, int W, const double *P, long long ld, int num_params, double *dl, long long ld_field,
                      long long ld_walker, int *fail_flags, hipStream_t stream);
+void theorycalc_set_derived(cmbt *t, const cmbt_derived_config_t *cfg);
+void theorycalc_derived_eval(cmbt *t, int M, const double *P, long long ld, int num_params, double *out,
+                             long long ld_out, int *fail_flags, hipStream_t stream);
 }  // namespace cmamd

@@ -10,44 +10,67 @@
 // no throughput against v_mfma_f64_16x16x4f64 and keeps the summation order
 // plain: a walker's bits depend on neither W, its place in the batch nor the
 // strides, and the zero padding of k adds exact zeros.
+//
+// Derived parameters (cmbt_set_derived / cmbt_derived_eval): up to 32 scalar
+// surfaces over the same monomials, summed by the same chain, in a kernel of
+// their own (theory_derived_kernel) tiled for few outputs and many points.
+#include <algorithm>
 #include <cstdint>
+#include <limits>
 
 #include "theorycalc.h"
 
 namespace cmamd {
 
-struct TheoryCalcArgs {
+// What a kernel needs to form the monomials of a tile of points
+struct TheoryBasisArgs {
     const double *meta;                  // [4][TC_MAXIN]: lo, hi, center, scale
-    const int *pidx, *fields;
+    const int *pidx;
     const unsigned long long *expo;      // [Kp] 4 bits per input, input 0 lowest
-    const double *coef;                  // [n_fields][Kp][Lp]
-    int n_in, K, Kp, lmax, Lp, ntl, W;
+    int n_in, K, Kp, W;
     const double *P;
     long long ld;
+};
+
+struct TheoryCalcArgs {
+    TheoryBasisArgs b;
+    const int *fields;
+    const double *coef;                  // [n_fields][Kp][Lp]
+    int lmax, Lp, ntl;
     double *dl;
     long long ld_field, ld_walker;
     int *fail;
 };
 
-// Workgroup (x: field j and l tile, y: walker tile): TC_TW walkers x TC_TN l.
-// Thread t holds 8 walkers (its wave's) x 4 l (2 * lane, + 1 and the same 128
-// further on), so a wave stores two 1 KB runs of consecutive l per walker row.
-__global__ __launch_bounds__(TC_THREADS) void theory_calc_kernel(TheoryCalcArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    double *Bs = lds;                              // [Kp][TC_TW] monomials
-    double *Cs = Bs + (size_t)a.Kp * TC_TW;        // [TC_KC][TC_TN] coefficient chunk
-    double *xs = Cs;                               // before the first chunk: [n_in][TC_TW] scaled inputs
-    const int t = threadIdx.x;
-    const int w0 = blockIdx.y * TC_TW;
-    const int j = blockIdx.x / a.ntl, l0 = (blockIdx.x % a.ntl) * TC_TN;
+struct TheoryDerivedArgs {
+    TheoryBasisArgs b;
+    const double *dcoef;                 // [Kp][TD_ND]
+    const double *dlim;                  // [2][TD_ND] lo, hi; null: no range test
+    int nd;
+    double *out;                         // [nd][ld_out]; null: the flags only
+    long long ld_out;
+    int *fail;
+};
 
+// Box test and monomials of points w0 .. w0 + TW - 1 by the NT threads of a
+// workgroup, for both kernels (xs [n_in][TW]: LDS for the scaled inputs).
+// Each pass forms NT / TW terms: thread t hands term k = k0 + t / TW of point
+// w0 + t % TW to sink(k, point in tile, value), its k ascending up to Kp.
+// With NT == TW a thread owns one point and k is uniform (scalar exponent
+// loads and loops).  Returns, in thread t < TW, whether point w0 + t fails the
+// box; no barrier after the last sink.
+template <int TW, int NT, class Sink>
+__device__ __forceinline__ int tc_basis_tile(const TheoryBasisArgs &a, int w0, double *xs, Sink &&sink)
+{
+    static_assert(NT % TW == 0, "whole terms per pass");
+    constexpr int KS = NT / TW;
+    const int t = threadIdx.x;
+    int bad = 0;
     // validity box on the raw parameters (equality passes, NaN fails); a failed
     // walker is evaluated at its inputs clamped into the box (NaN: the centre),
     // so the buffer never holds junk
-    if (t < TC_TW) {
+    if (t < TW) {
         const int w = w0 + t;
-        int bad = 0;
         for (int i = 0; i < a.n_in; i++) {
             double x = 0.0;
             if (w < a.W) {
@@ -61,25 +84,46 @@ __global__ __launch_bounds__(TC_THREADS) void theory_calc_kernel(TheoryCalcArgs 
                 }
                 x = (p - c) / s;
             }
-            xs[i * TC_TW + t] = x;
+            xs[i * TW + t] = x;
         }
-        if (a.fail && blockIdx.x == 0 && w < a.W) a.fail[w] = bad;
     }
     __syncthreads();
     // basis_k = prod_i x_i^e_ki from 1.0, inputs ascending, powers by repeated multiplication
-    for (int idx = t; idx < a.Kp * TC_TW; idx += TC_THREADS) {
-        const int k = idx / TC_TW, wl = idx % TC_TW;
+    const int wl = KS == 1 ? t : t % TW, kq = KS == 1 ? 0 : t / TW;
+    for (int k0 = 0; k0 < a.Kp; k0 += KS) {        // (Kp is a multiple of TC_KC, and so of KS)
+        const int k = k0 + kq;
         double b = 0.0;                            // the padding of k: exact zeros
         if (k < a.K) {
             unsigned long long e = a.expo[k];
             b = 1.0;
             for (int i = 0; i < a.n_in; i++, e >>= 4) {
-                const double x = xs[i * TC_TW + wl];
+                const double x = xs[i * TW + wl];
                 for (int r = (int)(e & 15); r > 0; r--) b *= x;
             }
         }
-        Bs[idx] = b;
+        sink(k, wl, b);
     }
+    return bad;
+}
+
+// Workgroup (x: field j and l tile, y: walker tile): TC_TW walkers x TC_TN l.
+// Thread t holds 8 walkers (its wave's) x 4 l (2 * lane, + 1 and the same 128
+// further on), so a wave stores two 1 KB runs of consecutive l per walker row.
+__global__ __launch_bounds__(TC_THREADS) void theory_calc_kernel(TheoryCalcArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const int Kp = a.b.Kp;
+    double *Bs = lds;                              // [Kp][TC_TW] monomials
+    double *Cs = Bs + (size_t)Kp * TC_TW;          // [TC_KC][TC_TN] coefficient chunk
+    double *xs = Cs;                               // before the first chunk: [n_in][TC_TW] scaled inputs
+    const int t = threadIdx.x;
+    const int w0 = blockIdx.y * TC_TW;
+    const int j = blockIdx.x / a.ntl, l0 = (blockIdx.x % a.ntl) * TC_TN;
+
+    static_assert(TC_KC % (TC_THREADS / TC_TW) == 0, "the terms of a pass divide the padding of K");
+    const int bad =
+        tc_basis_tile<TC_TW, TC_THREADS>(a.b, w0, xs, [&](int k, int wl, double b) { Bs[k * TC_TW + wl] = b; });
+    if (t < TC_TW && a.fail && blockIdx.x == 0 && w0 + t < a.b.W) a.fail[w0 + t] = bad;
 
     const int lane = t & 63, wv = t >> 6;
     double acc[8][4];
@@ -89,7 +133,7 @@ __global__ __launch_bounds__(TC_THREADS) void theory_calc_kernel(TheoryCalcArgs 
         for (int q = 0; q < 4; q++) acc[r][q] = 0.0;
     // chunk loads: TC_KC rows x TC_TN doubles = 4 double2 a thread, the next
     // chunk fetched into registers while this one is multiplied
-    const double *Cg = a.coef + (size_t)j * a.Kp * a.Lp + l0;
+    const double *Cg = a.coef + (size_t)j * Kp * a.Lp + l0;
     constexpr int C2 = TC_TN / 2;                  // double2 per chunk row
     constexpr int NPRE = TC_KC * C2 / TC_THREADS;
     static_assert(NPRE == 4, "four double2 of the chunk a thread");
@@ -104,14 +148,14 @@ __global__ __launch_bounds__(TC_THREADS) void theory_calc_kernel(TheoryCalcArgs 
     double2 p0, p1, p2, p3;
     TC_FETCH(0)
     double2 *Cs2 = reinterpret_cast<double2 *>(Cs);
-    for (int k0 = 0; k0 < a.Kp; k0 += TC_KC) {
+    for (int k0 = 0; k0 < Kp; k0 += TC_KC) {
         __syncthreads();                           // xs / the previous chunk have been read
         Cs2[t] = p0;
         Cs2[t + TC_THREADS] = p1;
         Cs2[t + 2 * TC_THREADS] = p2;
         Cs2[t + 3 * TC_THREADS] = p3;
         __syncthreads();
-        if (k0 + TC_KC < a.Kp) {
+        if (k0 + TC_KC < Kp) {
             TC_FETCH(k0 + TC_KC)
         }
 #pragma unroll
@@ -137,7 +181,7 @@ __global__ __launch_bounds__(TC_THREADS) void theory_calc_kernel(TheoryCalcArgs 
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         const int w = w0 + wv * 8 + r;
-        if (w < a.W) {
+        if (w < a.b.W) {
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 const int l = l0 + h * (TC_TN / 2) + 2 * lane;
@@ -154,7 +198,49 @@ __global__ __launch_bounds__(TC_THREADS) void theory_calc_kernel(TheoryCalcArgs 
     }
 }
 
+// Derived outputs out[d][m] = sum_k basis_k(m) dcoef[k][d]: the same monomials
+// and the same fma chain as theory_calc_kernel, so an output whose coefficients
+// are a D_l column has that D_l's bits.  A thread owns one point and all its
+// outputs (up to 32 accumulators in registers, in groups of 8 behind uniform
+// branches); term k is uniform over the workgroup, so its exponents and its
+// coefficient row come by scalar loads and a monomial costs a thread its
+// n_in LDS reads and at most 4 multiplications for up to 32 fma.  LDS holds
+// only the scaled inputs (n_in x 2 KB), so a CU keeps several workgroups.
+// Output rows are stored in 2 KB runs of consecutive points.
+__global__ __launch_bounds__(TD_THREADS) void theory_derived_kernel(TheoryDerivedArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];   // [n_in][TD_TM] scaled inputs
+    const int m = blockIdx.x * TD_TM + threadIdx.x;
+    const int ng = (a.nd + 7) >> 3;                // groups of 8 outputs in use
+    const double *__restrict__ dcoef = a.dcoef;
+    double acc[TD_ND];
+#pragma unroll
+    for (int d = 0; d < TD_ND; d++) acc[d] = 0.0;
+#define TD_GROUP(g)                                                                              \
+    _Pragma("unroll") for (int q = 8 * (g); q < 8 * (g) + 8; q++) acc[q] = __builtin_fma(b, c[q], acc[q]);
+    const int bad = tc_basis_tile<TD_TM, TD_THREADS>(a.b, blockIdx.x * TD_TM, lds, [&](int k, int, double b) {
+        const double *__restrict__ c = dcoef + (size_t)k * TD_ND;
+        TD_GROUP(0)
+        if (ng > 1) { TD_GROUP(1) }
+        if (ng > 2) { TD_GROUP(2) }
+        if (ng > 3) { TD_GROUP(3) }
+    });
+#undef TD_GROUP
+    if (m >= a.b.W) return;
+    // range test lo <= v <= hi (equality passes, NaN fails) and the stores
+    int out_of_range = 0;
+#pragma unroll
+    for (int d = 0; d < TD_ND; d++) {
+        if (d < a.nd) {
+            if (a.dlim && !(acc[d] >= a.dlim[d] && acc[d] <= a.dlim[TD_ND + d])) out_of_range = 1;
+            if (a.out) a.out[(long long)d * a.ld_out + m] = acc[d];
+        }
+    }
+    if (a.fail) a.fail[m] = bad | out_of_range;
+}
+
 static size_t tc_lds_bytes(int Kp) { return ((size_t)Kp * TC_TW + (size_t)TC_KC * TC_TN) * 8; }
+static size_t td_lds_bytes(int n_in) { return (size_t)n_in * TD_TM * 8; }
 
 void theorycalc_create(cmbt *t, const cmbt_config_t *c) {
     if (c->n_in < 1 || c->n_in > TC_MAXIN) fail(CMBL_ERR_ARG, "cmbt_create: n_in must be in 1..%d", TC_MAXIN);
@@ -217,6 +303,38 @@ void theorycalc_create(cmbt *t, const cmbt_config_t *c) {
                                   (int)tc_lds_bytes(TC_MAXTERMS)));
 }
 
+static TheoryBasisArgs basis_args(const cmbt *t, int W, const double *P, long long ld) {
+    TheoryBasisArgs b{};
+    b.meta = t->meta.as<double>();
+    b.pidx = t->pidx_d.as<int>();
+    b.expo = t->expo.as<unsigned long long>();
+    b.n_in = t->n_in;
+    b.K = t->K;
+    b.Kp = t->Kp;
+    b.W = W;
+    b.P = P;
+    b.ld = ld;
+    return b;
+}
+
+// out == nullptr: the failure flags only
+static void launch_derived(cmbt *t, int M, const double *P, long long ld, double *out, long long ld_out,
+                           int *fail_flags, hipStream_t stream) {
+    TheoryDerivedArgs a{};
+    a.b = basis_args(t, M, P, ld);
+    a.dcoef = t->dcoef.as<double>();
+    a.dlim = t->ranged ? t->dlim.as<double>() : nullptr;
+    a.nd = t->n_derived;
+    a.out = out;
+    a.ld_out = ld_out;
+    a.fail = fail_flags;
+    timed_launch("theory_derived_kernel", stream, [&](hipEvent_t e0, hipEvent_t e1) {
+        hipExtLaunchKernelGGL(theory_derived_kernel, dim3((M + TD_TM - 1) / TD_TM), dim3(TD_THREADS),
+                              td_lds_bytes(t->n_in), stream, e0, e1, 0, a);
+    });
+    HIP_CHECK(hipGetLastError());
+}
+
 void theorycalc_eval(cmbt *t, int W, const double *P, long long ld, int num_params, double *dl, long long ld_field,
                      long long ld_walker, int *fail_flags, hipStream_t stream) {
     if (W <= 0) fail(CMBL_ERR_ARG, "cmbt_eval: W must be positive");
@@ -227,20 +345,12 @@ void theorycalc_eval(cmbt *t, int W, const double *P, long long ld, int num_para
     if (ld_walker == 0) fail(CMBL_ERR_ARG, "cmbt_eval: per-walker theory rows needed (ld_walker != 0)");
     if (ld_field < t->lmax + 1) fail(CMBL_ERR_ARG, "cmbt_eval: ld_field %lld below lmax + 1 = %d", ld_field, t->lmax + 1);
     TheoryCalcArgs a{};
-    a.meta = t->meta.as<double>();
-    a.pidx = t->pidx_d.as<int>();
+    a.b = basis_args(t, W, P, ld);
     a.fields = t->fields_d.as<int>();
-    a.expo = t->expo.as<unsigned long long>();
     a.coef = t->coef.as<double>();
-    a.n_in = t->n_in;
-    a.K = t->K;
-    a.Kp = t->Kp;
     a.lmax = t->lmax;
     a.Lp = t->Lp;
     a.ntl = t->Lp / TC_TN;
-    a.W = W;
-    a.P = P;
-    a.ld = ld;
     a.dl = dl;
     a.ld_field = ld_field;
     a.ld_walker = ld_walker;
@@ -250,6 +360,51 @@ void theorycalc_eval(cmbt *t, int W, const double *P, long long ld, int num_para
         hipExtLaunchKernelGGL(theory_calc_kernel, grid, dim3(TC_THREADS), tc_lds_bytes(t->Kp), stream, e0, e1, 0, a);
     });
     HIP_CHECK(hipGetLastError());
+    // with ranges set the flags take the range test in as well: the derived
+    // kernel, storing no output, writes box-or-range over the box flags in
+    // stream order
+    if (t->ranged && fail_flags) launch_derived(t, W, P, ld, nullptr, 0, fail_flags, stream);
+}
+
+void theorycalc_set_derived(cmbt *t, const cmbt_derived_config_t *c) {
+    if (!c) {
+        t->n_derived = 0;
+        t->ranged = false;
+        t->dcoef.release();
+        t->dlim.release();
+        return;
+    }
+    if (c->n_derived < 1 || c->n_derived > TD_ND)
+        fail(CMBL_ERR_ARG, "cmbt_set_derived: n_derived must be in 1..%d", TD_ND);
+    if (!c->coef) fail(CMBL_ERR_ARG, "cmbt_set_derived: null coefficient table");
+    const int nd = c->n_derived;
+    const double inf = std::numeric_limits<double>::infinity();
+    std::vector<double> lim(2 * TD_ND);
+    for (int d = 0; d < TD_ND; d++) {
+        lim[d] = c->lo && d < nd ? c->lo[d] : -inf;
+        lim[TD_ND + d] = c->hi && d < nd ? c->hi[d] : inf;
+        if (!(lim[d] <= lim[TD_ND + d])) fail(CMBL_ERR_ARG, "cmbt_set_derived: output %d has lo > hi", d);
+    }
+    std::vector<double> coef((size_t)t->Kp * TD_ND, 0.0);
+    for (int k = 0; k < t->K; k++)
+        std::copy(c->coef + (size_t)k * nd, c->coef + (size_t)(k + 1) * nd, coef.begin() + (size_t)k * TD_ND);
+    upload(t->dcoef, coef);
+    upload(t->dlim, lim);
+    t->n_derived = nd;
+    t->ranged = c->lo || c->hi;
+}
+
+void theorycalc_derived_eval(cmbt *t, int M, const double *P, long long ld, int num_params, double *out,
+                             long long ld_out, int *fail_flags, hipStream_t stream) {
+    if (t->n_derived == 0) fail(CMBL_ERR_ARG, "cmbt_derived_eval: no derived outputs set (cmbt_set_derived)");
+    if (M <= 0 || M > std::numeric_limits<int>::max() - TD_TM)
+        fail(CMBL_ERR_ARG, "cmbt_derived_eval: M must be in 1..%d", std::numeric_limits<int>::max() - TD_TM);
+    if (!P || !out) fail(CMBL_ERR_ARG, "cmbt_derived_eval: null buffer");
+    if (ld < M) fail(CMBL_ERR_ARG, "cmbt_derived_eval: ld %lld below M %d", ld, M);
+    if (ld_out < M) fail(CMBL_ERR_ARG, "cmbt_derived_eval: ld_out %lld below M %d", ld_out, M);
+    for (int p : t->pidx)
+        if (p > num_params) fail(CMBL_ERR_ARG, "cmbt_derived_eval: param_index %d outside 1..%d", p, num_params);
+    launch_derived(t, M, P, ld, out, ld_out, fail_flags, stream);
 }
 
 }  // namespace cmamd

@@ -14,6 +14,13 @@ theory source, so slow steps need no host callback.
 
 ``monomials`` and ``fit_coefficients`` are pure numpy: the surface is fitted
 offline from theory computed elsewhere (e.g. CAMB at a design of points).
+
+Derived parameters (the parameterization's H0, omegam, sigma8, ..., DL40 ..
+DL2000 of the reference's chain rows, CosmologyParameterizations.f90:189-272)
+are scalar surfaces over the same monomials, ``derived_d = sum_k basis_k *
+dcoef[k, d]`` (``fit_derived``, ``dl_columns``, ``set_derived``,
+``derived``); their hard ranges are TP_NonBaseParameterPriors' cuts (:90-112):
+a point whose derived value leaves its range fails like one outside the box.
 """
 from __future__ import annotations
 
@@ -75,6 +82,33 @@ def fit_coefficients(points, theory, exponents, center, scale):
     return sol.reshape(B.shape[1], th.shape[1], th.shape[2]), resid
 
 
+def fit_derived(points, values, exponents, center, scale):
+    """Least-squares fit of scalar surfaces over the calculator's monomials:
+    points [M, n_in] (raw parameters), values [M, n_derived] (e.g. H0, sigma8
+    at the points).  Returns (coef [K, n_derived], the maximum absolute
+    residual), as fit_coefficients."""
+    v = np.asarray(values, dtype=np.float64)
+    if v.ndim != 2:
+        raise ValueError("values must be [M, n_derived]")
+    coef, resid = fit_coefficients(points, v[:, None, :], exponents, center, scale)
+    return np.ascontiguousarray(coef[:, 0, :]), resid
+
+
+def dl_columns(coef, field_pos, ells):
+    """Derived-output coefficients [K, n] that reproduce D_l bit for bit:
+    column i is coef[:, field_pos[i], ells[i]] of the calculator's table
+    [K, n_fields, lmax + 1] (field_pos: positions in the calculator's field
+    list; a scalar applies to every l) -- the reference's DL40 .. DL2000."""
+    coef = np.asarray(coef, dtype=np.float64)
+    if coef.ndim != 3:
+        raise ValueError("coef must be [n_terms, n_fields, lmax + 1]")
+    ells = np.asarray(ells, dtype=np.int64).reshape(-1)
+    pos = np.broadcast_to(np.asarray(field_pos, dtype=np.int64), ells.shape)
+    if np.any(pos < 0) or np.any(pos >= coef.shape[1]) or np.any(ells < 0) or np.any(ells >= coef.shape[2]):
+        raise ValueError("field position or l outside the coefficient table")
+    return np.ascontiguousarray(coef[:, pos, ells])
+
+
 class PolynomialTheory:
     """A ``cmbt_t``.  param_index: 1-based indices into P of the n_in inputs;
     lo, hi: the validity box on the raw parameters; exponents [K, n_in];
@@ -109,6 +143,7 @@ class PolynomialTheory:
         self.handle = h
         self.n_in, self.n_terms, self.lmax = n_in, coef.shape[0], coef.shape[2] - 1
         self.fields = fl.tolist()
+        self.derived_names, self.derived_ranges = [], []     # [(name, label)], [(name, lo or None, hi or None)]
 
     def eval(self, P_rows, out, fail=None, stream=None):
         """Evaluate into ``out``, a cuda float64 theory tensor [W, n_field_rows, L]
@@ -120,10 +155,7 @@ class PolynomialTheory:
         fail: a cuda int32 tensor [W] that receives 1 for the walkers outside
         the box (which are evaluated at their clamped inputs), else 0."""
         import torch
-        if not torch.is_tensor(P_rows):
-            P_rows = torch.as_tensor(np.ascontiguousarray(np.asarray(P_rows, dtype=np.float64).T), device="cuda")
-        if P_rows.dim() != 2 or P_rows.dtype != torch.float64 or (P_rows.shape[1] > 1 and P_rows.stride(1) != 1):
-            raise ValueError("P_rows must be float64 [num_params, W] with walker stride 1")
+        P_rows, ld = self._rows(P_rows)
         num_params, W = P_rows.shape
         if out.dim() != 3 or out.dtype != torch.float64 or out.shape[0] != W or out.stride(2) != 1:
             raise ValueError("out must be float64 [W, fields, L] with last stride 1")
@@ -134,10 +166,83 @@ class PolynomialTheory:
             raise ValueError("fail must be a contiguous int32 tensor [W]")
         if stream is None:
             stream = N.current_stream_ptr()
-        ld = P_rows.stride(0) if num_params > 1 else max(W, P_rows.stride(0))
         N.check(N.lib().cmbt_eval(self.handle, W, P_rows.data_ptr(), ld, num_params, out.data_ptr(), out.stride(1),
                                   out.stride(0), None if fail is None else fail.data_ptr(), stream),
                 self.handle, "cmbt")
+
+    def set_derived(self, names, coef, lo=None, hi=None, labels=None):
+        """Calculator-derived parameters (``cmbt_set_derived``): ``names`` of
+        the n_derived <= 32 outputs, coef [n_terms, n_derived] over the
+        calculator's monomials (fit_derived, dl_columns); lo / hi: hard ranges
+        per output (None or +-inf: no limit on that side).  With a range set,
+        eval's fail flags -- and so the sampler's slow steps -- also reject a
+        point whose output leaves its range (TP_NonBaseParameterPriors'
+        cuts).  names=None removes the derived outputs."""
+        self.derived_names, self.derived_ranges = [], []
+        if names is None:
+            N.check(N.lib().cmbt_set_derived(self.handle, None), self.handle, "cmbt")
+            return
+        names = [str(n) for n in names]
+        coef = np.ascontiguousarray(coef, dtype=np.float64)
+        if coef.ndim != 2 or coef.shape[0] != self.n_terms or coef.shape[1] != len(names):
+            raise ValueError(f"coef must be [n_terms = {self.n_terms}, n_derived = {len(names)}]")
+        labels = list(labels) if labels is not None else names
+        if len(labels) != len(names):
+            raise ValueError("labels need one entry per name")
+        dp = C.POINTER(C.c_double)
+        cfg = N.CmbtDerivedConfig()
+        cfg.n_derived, cfg.coef = len(names), coef.ctypes.data_as(dp)
+        lims = []
+        for side, fill in ((lo, -np.inf), (hi, np.inf)):
+            if side is None:
+                lims.append(None)
+                continue
+            a = np.array([fill if v is None else v for v in side], dtype=np.float64).reshape(-1)
+            if a.size != len(names):
+                raise ValueError("lo and hi need one entry per name")
+            lims.append(a)
+        cfg.lo = lims[0].ctypes.data_as(dp) if lims[0] is not None else None
+        cfg.hi = lims[1].ctypes.data_as(dp) if lims[1] is not None else None
+        N.check(N.lib().cmbt_set_derived(self.handle, C.byref(cfg)), self.handle, "cmbt")
+        self.derived_names = list(zip(names, labels))
+        for k, n in enumerate(names):
+            mn = None if lims[0] is None or not np.isfinite(lims[0][k]) else float(lims[0][k])
+            mx = None if lims[1] is None or not np.isfinite(lims[1][k]) else float(lims[1][k])
+            self.derived_ranges.append((n, mn, mx))
+
+    def derived(self, P_rows, out=None, fail=None, stream=None):
+        """The derived outputs at P_rows (the forms eval accepts): a cuda
+        float64 tensor [n_derived, M] (``out``, last stride 1, when given).
+        fail: a cuda int32 tensor [M] that receives 1 for the points outside
+        the box or, with ranges set, outside a range."""
+        import torch
+        P_rows, ld = self._rows(P_rows)
+        num_params, M = P_rows.shape
+        nd = N.lib().cmbt_derived_count(self.handle)
+        if out is None:
+            out = torch.empty((max(nd, 1), M), dtype=torch.float64, device="cuda")[:nd]
+        if out.dim() != 2 or out.dtype != torch.float64 or out.shape != (nd, M) or (M > 1 and out.stride(1) != 1):
+            raise ValueError(f"out must be float64 [{nd}, {M}] with last stride 1")
+        if fail is not None and (fail.dtype != torch.int32 or fail.numel() < M or not fail.is_contiguous()):
+            raise ValueError("fail must be a contiguous int32 tensor [M]")
+        if stream is None:
+            stream = N.current_stream_ptr()
+        ld_out = out.stride(0) if nd > 1 else max(M, out.stride(0))
+        N.check(N.lib().cmbt_derived_eval(self.handle, M, P_rows.data_ptr(), ld, num_params, out.data_ptr(), ld_out,
+                                          None if fail is None else fail.data_ptr(), stream),
+                self.handle, "cmbt")
+        return out
+
+    @staticmethod
+    def _rows(P_rows):
+        """(cuda float64 rows [num_params, M] with point stride 1, their ld)"""
+        import torch
+        if not torch.is_tensor(P_rows):
+            P_rows = torch.as_tensor(np.ascontiguousarray(np.asarray(P_rows, dtype=np.float64).T), device="cuda")
+        if P_rows.dim() != 2 or P_rows.dtype != torch.float64 or (P_rows.shape[1] > 1 and P_rows.stride(1) != 1):
+            raise ValueError("P_rows must be float64 [num_params, W] with walker stride 1")
+        num_params, W = P_rows.shape
+        return P_rows, (P_rows.stride(0) if num_params > 1 else max(W, P_rows.stride(0)))
 
     def close(self):
         if getattr(self, "handle", None):

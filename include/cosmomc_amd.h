@@ -23,6 +23,10 @@
  *   cmbt_*               the calculator object's theory at a slow point, as a polynomial
  *                        response surface of D_l (the slot of source/Calculator_PICO.f90;
  *                        error = 1 outside the box -> logZero, calclike.f90:308-313)
+ *   cmbt_set_derived / cmbt_derived_eval
+ *                        the parameterization's derived parameters (TP_CalcDerivedParams,
+ *                        source/CosmologyParameterizations.f90:189-272) as response surfaces,
+ *                        and TP_NonBaseParameterPriors' hard cuts on them (:90-112)
  *   cmbs_*               BlockedProposer (source/propose.f90:53-298) + Metropolis
  *                        (source/MCMC.f90:119-335) + GetLogLike bounds/priors/temperature
  *                        (source/calclike.f90:82-151), batched over W independent chains
@@ -311,6 +315,46 @@ const char *cmbt_last_error(const cmbt_t *t);
  * ld_walker == 0 or ld_field < lmax + 1. */
 int  cmbt_eval(cmbt_t *t, int W, const double *P, long long ld, int num_params,
                double *dl, long long ld_field, long long ld_walker, int *fail, void *stream);
+/* Calculator-derived parameters: scalar response surfaces over the same
+ * monomials, the parameterization's derived parameters of the reference's chain
+ * rows (H0, omegam, sigma8, ..., DL40 .. DL2000: CosmologyParameterizations.f90:
+ * 189-272, calclike.f90:447-448) and the hard cuts of TP_NonBaseParameterPriors
+ * (CosmologyParameterizations.f90:90-112: logZero when H0 leaves [H0_min,
+ * H0_max] or zre < use_min_zre, before any likelihood runs, calclike.f90:300-301).
+ *
+ *   out[d*ld_out + m] = sum_k basis_k(m) * coef[k][d],  d = 0..n_derived-1,
+ * with the box test, clamp, monomials and fma chain of cmbt_eval: an output
+ * whose coef column is a D_l coefficient column has cmbt_eval's bits of that
+ * D_l, and a point's bits depend on neither M, its place nor the strides.
+ * With lo or hi given the outputs are ranged: a point fails when any output
+ * violates lo_d <= v <= hi_d (equality passes; a NaN value fails, also against
+ * infinite limits).  With both NULL there is no range test. */
+#define CMBT_MAXDERIVED 32
+typedef struct {
+    int n_derived;            /* 1..CMBT_MAXDERIVED */
+    const double *coef;       /* host [n_terms][n_derived] */
+    const double *lo, *hi;    /* n_derived each, or NULL = none; -inf / +inf = no limit on that side */
+} cmbt_derived_config_t;
+/* Copies the tables; replaces an earlier set; cfg == NULL removes it, and the
+ * calculator is again exactly what cmbt_create made.  CMBL_ERR_ARG for
+ * n_derived outside 1..32, a NULL coef, or lo > hi.  Not to be called while
+ * work that uses the calculator is in flight. */
+int  cmbt_set_derived(cmbt_t *t, const cmbt_derived_config_t *cfg);
+int  cmbt_derived_count(const cmbt_t *t);
+/* One launch (theory_derived_kernel), asynchronous on `stream`, for M points:
+ *   P     device rows [num_params][ld], point-minor, as for cmbt_eval
+ *   out   device [n_derived][ld_out], point-minor
+ *   fail  device int[M]: 1 for a point outside the box (its outputs are those
+ *         of the clamped inputs) or, when ranged, with an output outside its
+ *         range; else 0; or NULL
+ * CMBL_ERR_ARG with nothing set, for ld < M, ld_out < M or a param_index
+ * outside 1..num_params.
+ * Once ranges are set, cmbt_eval's own fail flags are box-or-range as well (a
+ * second small launch in stream order; the D_l it writes keeps every bit), so
+ * a sampler with this calculator rejects such trials as logZero and
+ * cmbs_refresh_theory refuses such current points. */
+int  cmbt_derived_eval(cmbt_t *t, int M, const double *P, long long ld, int num_params,
+                       double *out, long long ld_out, int *fail, void *stream);
 /* The calculator as the sampler's theory source: with theory_fn == NULL,
  * cmbs_step_theory and cmbs_step_drag evaluate it at the trial rows into every
  * distinct trial-theory buffer (cmbs_set_trial_theory), one launch each and

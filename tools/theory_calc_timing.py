@@ -10,6 +10,11 @@
           plik_lite problem with theory = A x base: the torch callback
           (trial = base x A, one host call per step) against the one-term
           calculator (no callback), alternating in one process.
+  derived cmbt_derived_eval at M = 1024 x 1000 points (a chain block), K = 210,
+          24 outputs, next to cmbt_eval of the same 24 columns as one field of
+          lmax 23 (theory_calc_kernel's 256-wide l tile on a padded table) for
+          the same M: device times from the library's own launch events
+          (cmbl_profile_*), and whether the two give the same bits.
 
 Without --part each part runs in a child process of its own under a time
 limit, and a part that fails stops the run.  Results: one JSON line per part
@@ -129,16 +134,55 @@ def part_steps():
             "native_over_callback": round(med["native"] / med["callback"], 4), "same_chains": same}
 
 
+def part_derived():
+    import numpy as np
+    import torch
+    from cosmomc_amd import _native as N
+    from cosmomc_amd import theory as th
+    rng = np.random.default_rng(2)
+    n_in, M, nd = 6, 1024 * 1000, 24
+    ex = th.monomials(n_in, 4)
+    K = len(ex)
+    center, scale = np.zeros(n_in), np.ones(n_in)
+    coef = rng.normal(size=(K, 1, nd))
+    calc = th.PolynomialTheory(list(range(1, n_in + 1)), center, scale, -2 * scale, 2 * scale, ex, [0], coef)
+    P = torch.tensor(rng.uniform(-1.0, 1.0, size=(n_in, M)), device="cuda")
+    out = torch.zeros((nd, M), dtype=torch.float64, device="cuda")
+    dl = torch.zeros((M, 1, nd), dtype=torch.float64, device="cuda")
+    fail = torch.zeros(M, dtype=torch.int32, device="cuda")
+    calc.set_derived([f"d{i}" for i in range(nd)], coef[:, 0, :])        # no range: cmbt_eval is one launch
+    res = {}
+    for name, fn in (("theory_derived_kernel", lambda: calc.derived(P, out=out, fail=fail)),
+                     ("theory_calc_kernel", lambda: calc.eval(P, dl, fail))):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        N.profile_reset()
+        N.profile_enable(True)
+        for _ in range(10):
+            fn()
+        torch.cuda.synchronize()
+        N.profile_enable(False)
+        ms, n = N.profile_read(name)
+        res[name] = {"launches": n, "us": round(ms * 1e3 / max(n, 1), 1)}
+    same = bool(torch.equal(out.T, dl[:, 0, :]))
+    calc.close()
+    nbytes = (n_in + nd) * M * 8 + M * 4
+    return {"part": "derived", "M": M, "K": K, "n_derived": nd, "kernels": res, "same_bits": same,
+            "derived_TB_per_s": round(nbytes / res["theory_derived_kernel"]["us"] / 1e6, 3),
+            "derived_TFLOP_per_s": round(2.0 * M * K * nd / res["theory_derived_kernel"]["us"] / 1e6, 2)}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--part", choices=["kernel", "steps"])
+    ap.add_argument("--part", choices=["kernel", "steps", "derived"])
     ap.add_argument("--out", help="append the JSON lines to this file")
     ap.add_argument("--timeout", type=int, default=240, help="seconds for each part")
     a = ap.parse_args()
     if a.part:
-        print(json.dumps({"kernel": part_kernel, "steps": part_steps}[a.part]()), flush=True)
+        print(json.dumps({"kernel": part_kernel, "steps": part_steps, "derived": part_derived}[a.part]()), flush=True)
         return 0
-    for part in ("kernel", "steps"):
+    for part in ("kernel", "steps", "derived"):
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--part", part], stdout=subprocess.PIPE,
                            text=True, timeout=a.timeout)
         sys.stdout.write(r.stdout)
