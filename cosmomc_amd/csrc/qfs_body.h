@@ -21,12 +21,17 @@ static_assert(QFS_XS_D >= QF_MAXKB * QF_TILE, "X over an item's K range");
 static constexpr int QFS_LDS_DOUBLES = QFS_NBUF * QFS_BUF_D + QFS_XS_D + QF_TILE;
 
 // One operand buffer's 16 KB by LDS-DMA, 16 pieces of 1 KB, 4 a wave: either
-// the A tile at column k0 (dma_tile's layout), or 32 rows of the tile's raw
-// sums over the I panel (S rows w0 + 32 h .. + 31, columns col0 .. col0 + 63;
-// two rows a piece, the 16-byte chunk c of row r stored at chunk c ^ (r & 15)
-// so the epilogue's reads of one column by 16 rows spread over the banks).
-__device__ __forceinline__ void dma_next(double *buf, bool a_tile, const double *Arow, int k0, const double *Sw0,
-                                         int col0, int h, size_t Np, int wave, int lane)
+// the A tile at column k0 (dma_tile's layout), or 32 bins of the tile's raw
+// sums over the I panel (SI: bin-major S at the panel's first bin and the
+// tile's first walker; bins 32 h .. + 31, each 64 walkers = 512 contiguous
+// bytes; two bins a piece, an odd bin's 128-byte halves of each 256 bytes
+// swapped, i.e. its 16-byte chunk c stored at chunk c ^ 8).  The epilogue's
+// ds_read_b64 of bin c0 + lk, walker 16 wave + li then has, in each 32-lane
+// group (lk = 0, 1 or 2, 3), the even bin's 16 lanes on the 32 banks of one
+// 128-byte half of the bank row and the odd bin's on the other half: no two
+// lanes of a group share a bank.
+__device__ __forceinline__ void dma_next(double *buf, bool a_tile, const double *Arow, int k0, const double *SI, int h,
+                                         size_t Np, size_t Wp, int wave, int lane)
 {
 #pragma unroll
     for (int q = 0; q < 4; q++) {
@@ -36,7 +41,7 @@ __device__ __forceinline__ void dma_next(double *buf, bool a_tile, const double 
         // (selected by mask: a uniform branch here splits the block, and the
         // compiler's wait counts turn pessimistic across the joins)
         const uintptr_t pa = (uintptr_t)(Arow + (size_t)ra * Np + k0 + ((lane & 15) ^ swz(ra)) * 2);
-        const uintptr_t ps = (uintptr_t)(Sw0 + (size_t)rs * Np + col0 + ((lane & 31) ^ (rs & 15)) * 2);
+        const uintptr_t ps = (uintptr_t)(SI + (size_t)rs * Wp + ((lane & 31) ^ ((rs & 1) << 3)) * 2);
         const uintptr_t m = (uintptr_t)0 - (uintptr_t)a_tile;
         const double *src = (const double *)((pa & m) | (ps & ~m));
         __builtin_amdgcn_global_load_lds((gbl_void_t *)src, (lds_void_t *)(buf + piece * 128), 16, 0, 0);
@@ -84,15 +89,25 @@ __device__ __forceinline__ unsigned lds_addr(const double *p)
 
 // Loads the compiler does not see (no wait of its own): the caller waits
 // with a counted vmcnt and passes the registers through that asm.
-__device__ __forceinline__ void qfs_load4(const double *p, f64x2 (&v)[4])
+// A lane's 8 sums of a K step: its walker's bins k .. k + 7, Wp doubles apart
+// in the bin-major S.  p (uniform) is bin k0's row at the tile's first walker
+// and voff the lane's own byte offset into it ((8 lk Wp + n) * 8); one scalar
+// base per bin.  The 16 lanes li of each lk share a 128-byte line, so a load
+// instruction touches 4 whole lines.
+__device__ __forceinline__ void qfs_load8(const double *p, size_t Wp, unsigned voff, double (&v)[8])
 {
     asm volatile(
-        "global_load_dwordx4 %0, %4, off\n"
-        "global_load_dwordx4 %1, %4, off offset:16\n"
-        "global_load_dwordx4 %2, %4, off offset:32\n"
-        "global_load_dwordx4 %3, %4, off offset:48"
-        : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])
-        : "v"(p));
+        "global_load_dwordx2 %0, %8, %9\n"
+        "global_load_dwordx2 %1, %8, %10\n"
+        "global_load_dwordx2 %2, %8, %11\n"
+        "global_load_dwordx2 %3, %8, %12\n"
+        "global_load_dwordx2 %4, %8, %13\n"
+        "global_load_dwordx2 %5, %8, %14\n"
+        "global_load_dwordx2 %6, %8, %15\n"
+        "global_load_dwordx2 %7, %8, %16"
+        : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7])
+        : "v"(voff), "s"(p), "s"(p + Wp), "s"(p + 2 * Wp), "s"(p + 3 * Wp), "s"(p + 4 * Wp), "s"(p + 5 * Wp),
+          "s"(p + 6 * Wp), "s"(p + 7 * Wp));
 }
 
 __device__ __forceinline__ double qfs_load1(const double *p)
@@ -125,6 +140,7 @@ __device__ __forceinline__ void qfs_body_nj(double *smem, int item_ix, int tile,
     const int li = lane & 15, lk = lane >> 4;
     const QFSource &q = a.src;
     const int Np = q.Np, W = a.W;
+    const size_t Wp = (size_t)a.Wp;
     const int w0 = tile * QF_TILE;
     const QFItem it = q.items[item_ix];
     // unrolled: an asm load's registers are in flight into the next step, and a
@@ -134,7 +150,8 @@ __device__ __forceinline__ void qfs_body_nj(double *smem, int item_ix, int tile,
     const double *Arow = q.Ct + (size_t)(it.I * QF_TILE) * Np;
     double *xs = smem + QFS_NBUF * QFS_BUF_D;   // [nJ * 64] X over the item's K range
     double *xI = xs + QFS_XS_D;                 // [64] X over the I panel
-    const double *Sw0 = a.S + (size_t)w0 * Np;
+    const double *SK = a.S + (size_t)kbase0 * Wp + w0;              // the K range's first bin, the tile's first walker
+    const double *SI = a.S + (size_t)(it.I * QF_TILE) * Wp + w0;   // the I panel's
     const int n = 16 * wave + li;               // this lane's walker in the tile
     // The VGPR loads (the calibration, the raw sums) are inline asm waited for
     // by hand: beside LDS-DMA the compiler waits vmcnt(0) for any load of its
@@ -165,18 +182,21 @@ __device__ __forceinline__ void qfs_body_nj(double *smem, int item_ix, int tile,
     unsigned abase[4];
 #pragma unroll
     for (int u = 0; u < 4; u++) abase[u] = lds_addr(smem + li * BK + (((lk * 4 + u) ^ swz(li)) * 2));
-    const double *Srow = Sw0 + (size_t)(16 * wave + li) * Np + kbase0 + 8 * lk;
-    f64x2 sv[2][4];
+    const unsigned svoff = (unsigned)((8 * lk * Wp + n) * 8);
+    double sv[2][8];
     dma_tile(smem, Arow, Np, kbase0, wave, lane);
-    qfs_load4(Srow, sv[0]);
+    qfs_load8(SK, Wp, svoff, sv[0]);
     double c2 = 1.0, rc2 = 1.0;
     f64x4 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
-    auto step = [&](int s, f64x2 (&sv)[4], f64x2 (&sv_next)[4]) {
+    auto step = [&](int s, double (&sv)[8], double (&sv_next)[8]) {
         // step s's operands, the only loads in flight (the sums pass through the
         // wait, so nothing reads them before it)
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(sv[0]), "+v"(sv[1]), "+v"(sv[2]), "+v"(sv[3]) :: "memory");
+        asm volatile("s_waitcnt vmcnt(0)"
+                     : "+v"(sv[0]), "+v"(sv[1]), "+v"(sv[2]), "+v"(sv[3]), "+v"(sv[4]), "+v"(sv[5]), "+v"(sv[6]),
+                       "+v"(sv[7])
+                     :: "memory");
         if (s == 0) {
             asm volatile("" : "+v"(cv));
             const double cl = has_cal ? cv : 1.0;
@@ -192,19 +212,19 @@ __device__ __forceinline__ void qfs_body_nj(double *smem, int item_ix, int tile,
             qfs_x_reads(lds_addr(xs + s * BK + 8 * lk), x);
 #pragma unroll
             for (int u = 0; u < 4; u++) {
-                b[u].x = x[u].x - div_rn(sv[u].x, c2, rc2);
-                b[u].y = x[u].y - div_rn(sv[u].y, c2, rc2);
+                b[u].x = x[u].x - div_rn(sv[2 * u], c2, rc2);
+                b[u].y = x[u].y - div_rn(sv[2 * u + 1], c2, rc2);
             }
         }
         // the next step's A tile and sums, or at the last step the Delta_I rows
         // into the two buffers the K loop no longer needs
         if (s + 1 < nsteps) {
-            dma_next(smem + ((s + 1) % QFS_NBUF) * QFS_BUF_D, true, Arow, kbase0 + (s + 1) * BK, Sw0, 0, 0, Np, wave,
+            dma_next(smem + ((s + 1) % QFS_NBUF) * QFS_BUF_D, true, Arow, kbase0 + (s + 1) * BK, SI, 0, Np, Wp, wave,
                      lane);
-            qfs_load4(Srow + (s + 1) * BK, sv_next);
+            qfs_load8(SK + (size_t)((s + 1) * BK) * Wp, Wp, svoff, sv_next);
         } else {
-            dma_next(smem + ((s + 1) % QFS_NBUF) * QFS_BUF_D, false, Arow, 0, Sw0, it.I * QF_TILE, 0, Np, wave, lane);
-            dma_next(smem + ((s + 2) % QFS_NBUF) * QFS_BUF_D, false, Arow, 0, Sw0, it.I * QF_TILE, 1, Np, wave, lane);
+            dma_next(smem + ((s + 1) % QFS_NBUF) * QFS_BUF_D, false, Arow, 0, SI, 0, Np, Wp, wave, lane);
+            dma_next(smem + ((s + 2) % QFS_NBUF) * QFS_BUF_D, false, Arow, 0, SI, 1, Np, Wp, wave, lane);
         }
         const unsigned boff = (s % QFS_NBUF) * QFS_BUF_D * 8;
         const unsigned ab[4] = {abase[0] + boff, abase[1] + boff, abase[2] + boff, abase[3] + boff};
@@ -233,8 +253,10 @@ __device__ __forceinline__ void qfs_body_nj(double *smem, int item_ix, int tile,
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                            // both Delta_I halves landed
     // lane (li, lk)'s walker n takes Delta_I[n][16 t + lk + 4 r] in quadform_body's
-    // order; half h of the rows sits in buffer (nsteps + h) % 3
-    const double *raw = smem + ((nsteps + (n >> 5)) % QFS_NBUF) * QFS_BUF_D + (n & 31) * QF_TILE;
+    // order; bins 32 h .. + 31 sit in buffer (nsteps + h) % 3, an odd bin's
+    // (odd lk's) walkers at n ^ 16 (dma_next)
+    const double *raw[2] = {smem + (nsteps % QFS_NBUF) * QFS_BUF_D + (n ^ ((lk & 1) << 4)),
+                            smem + ((nsteps + 1) % QFS_NBUF) * QFS_BUF_D + (n ^ ((lk & 1) << 4))};
     const bool live = w0 + n < W;
     double sacc = 0.0;
 #pragma unroll
@@ -242,7 +264,7 @@ __device__ __forceinline__ void qfs_body_nj(double *smem, int item_ix, int tile,
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int c = 16 * t + lk + 4 * r;
-            const double sv = raw[(((c >> 1) ^ (n & 15)) << 1) | (c & 1)];
+            const double sv = raw[t >> 1][(c & 31) * QF_TILE];
             const double d = live ? xI[c] - div_rn(sv, c2, rc2) : 0.0;
             sacc += acc[t][r] * d;
         }
@@ -257,7 +279,8 @@ __device__ __forceinline__ void qfs_body_nj(double *smem, int item_ix, int tile,
 // The quadratic form's K loop with the compiler's own loads and waits (its
 // LDS-DMA wait is vmcnt(0) per step) and the Delta_I rows loaded after it:
 // items wider than two column blocks.
-static constexpr int QFSL_TILE_D = QF_TILE * (QF_TILE + 2);
+static constexpr int QFSL_ROW = QF_TILE + 16;
+static constexpr int QFSL_TILE_D = QF_TILE * QFSL_ROW;
 static_assert(QFSL_TILE_D + QF_TILE + QF_MAXKB * QF_TILE + QF_TILE <= QFS_LDS_DOUBLES, "the loop body's LDS");
 __device__ __forceinline__ void qfs_body_loop(double *smem, int item_ix, int tile, const QFSArgs &a)
 {
@@ -265,6 +288,7 @@ __device__ __forceinline__ void qfs_body_loop(double *smem, int item_ix, int til
     const int li = lane & 15, lk = lane >> 4;
     const QFSource &q = a.src;
     const int Np = q.Np, W = a.W;
+    const size_t Wp = (size_t)a.Wp;
     const int w0 = tile * QF_TILE;
     const QFItem it = q.items[item_ix];
     const int nsteps = it.nJ * (QF_TILE / BK);
@@ -274,10 +298,11 @@ __device__ __forceinline__ void qfs_body_loop(double *smem, int item_ix, int til
     double *xs = c2s + QF_TILE;                 // [nJ * 64] X over the item's K range
     double *xI = xs + QF_MAXKB * QF_TILE;       // [64] X over the I panel
     dma_tile(smem, Arow, Np, kbase0, wave, lane);
-    const double *Srow = a.S + (size_t)(w0 + 16 * wave + li) * Np + kbase0 + 8 * lk;
+    // this lane's walker's bins kbase0 + 8 lk .. + 7, Wp doubles apart
+    const double *Srow = a.S + (size_t)(kbase0 + 8 * lk) * Wp + w0 + 16 * wave + li;
     double2 sv[4];
 #pragma unroll
-    for (int u = 0; u < 4; u++) sv[u] = *reinterpret_cast<const double2 *>(Srow + 2 * u);
+    for (int u = 0; u < 4; u++) sv[u] = make_double2(Srow[(size_t)(2 * u) * Wp], Srow[(size_t)(2 * u + 1) * Wp]);
     if (tid < QF_TILE) {                        // the emit's c2 = cal * cal (walkers past W: never stored)
         const int wc = min(w0 + tid, W - 1);
         double cl = 1.0;
@@ -311,7 +336,9 @@ __device__ __forceinline__ void qfs_body_loop(double *smem, int item_ix, int til
         if (s + 1 < nsteps) {
             dma_tile(smem + (buf ^ 1) * QF_TILE * BK, Arow, Np, kbase0 + (s + 1) * BK, wave, lane);
 #pragma unroll
-            for (int u = 0; u < 4; u++) sv[u] = *reinterpret_cast<const double2 *>(Srow + (s + 1) * BK + 2 * u);
+            for (int u = 0; u < 4; u++)
+                sv[u] = make_double2(Srow[(size_t)((s + 1) * BK + 2 * u) * Wp],
+                                     Srow[(size_t)((s + 1) * BK + 2 * u + 1) * Wp]);
         }
         const double *A = smem + buf * QF_TILE * BK;
         double2 af[4][4];
@@ -332,24 +359,29 @@ __device__ __forceinline__ void qfs_body_loop(double *smem, int item_ix, int til
                 acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[t][u].y, b[u].y, acc[t], 0, 0, 0);
         }
     }
-    // Delta_I tile: smem[n][i] (row stride QF_TILE + 2), as quadform_body
+    // Delta_I tile, bin-major as S: smem[i][n], row stride QFSL_ROW (640 bytes: the
+    // reads below of bins c0 + lk by a 32-lane group's lk = 0, 1 or 2, 3 fall on
+    // the two 128-byte halves of the bank row)
     double2 dI[QF_TILE * QF_TILE / 2 / 256];
 #pragma unroll
     for (int u = 0; u < QF_TILE * QF_TILE / 2 / 256; u++) {
-        const int e = tid + 256 * u, r = e >> 5, c = (e & 31) * 2;
-        dI[u] = *reinterpret_cast<const double2 *>(a.S + (size_t)(w0 + r) * Np + it.I * QF_TILE + c);
+        const int e = tid + 256 * u, c = e >> 5, r = (e & 31) * 2;
+        dI[u] = *reinterpret_cast<const double2 *>(a.S + (size_t)(it.I * QF_TILE + c) * Wp + w0 + r);
     }
     __syncthreads();                            // every wave done with the operand buffers
 #pragma unroll
     for (int u = 0; u < QF_TILE * QF_TILE / 2 / 256; u++) {
-        const int e = tid + 256 * u, r = e >> 5, c = (e & 31) * 2;
+        const int e = tid + 256 * u, c = e >> 5, r = (e & 31) * 2;
         double2 v = make_double2(0.0, 0.0);
         if (w0 + r < W) {
             const double cr = c2s[r], rr = 1.0 / cr;
             v.x = xI[c] - div_rn(dI[u].x, cr, rr);
-            v.y = xI[c + 1] - div_rn(dI[u].y, cr, rr);
         }
-        *reinterpret_cast<double2 *>(smem + r * (QF_TILE + 2) + c) = v;
+        if (w0 + r + 1 < W) {
+            const double cr = c2s[r + 1], rr = 1.0 / cr;
+            v.y = xI[c] - div_rn(dI[u].y, cr, rr);
+        }
+        *reinterpret_cast<double2 *>(smem + c * QFSL_ROW + r) = v;
     }
     __syncthreads();
     const int n = 16 * wave + li;
@@ -357,7 +389,7 @@ __device__ __forceinline__ void qfs_body_loop(double *smem, int item_ix, int til
 #pragma unroll
     for (int t = 0; t < 4; t++)
 #pragma unroll
-        for (int r = 0; r < 4; r++) sacc += acc[t][r] * smem[n * (QF_TILE + 2) + 16 * t + lk + 4 * r];
+        for (int r = 0; r < 4; r++) sacc += acc[t][r] * smem[(16 * t + lk + 4 * r) * QFSL_ROW + n];
     sacc += __shfl_xor(sacc, 16);
     sacc += __shfl_xor(sacc, 32);
     if (lk == 0) {

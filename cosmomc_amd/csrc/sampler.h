@@ -246,7 +246,7 @@ struct cmbs {
     // else the bin co-run or the unpipelined steps), 0 unpipelined (debug /
     // A/B: CMAMD_PIPE, cmamd_debug_pipeline)
     int pipe_mode = 3;
-    cmamd::DevBuf tail_S[2][2];              // [parity][stage] the pass's raw sums
+    cmamd::DevBuf tail_S[2][2];              // [parity][stage] the pass's raw sums (kind 1: bin-major, steptail.h)
     cmamd::DevBuf tail_rowcal;               // the chi^2 stage's calibrated partial rows (SmallGaussLaunch::row_cal)
     int tail_ready = 0;                      // W it is set up for (0: not yet, -W: not possible)
     int tail_qf = -1, tail_g = -1;           // the stage (0 / 1) of the quadratic form / of the chi^2

@@ -1130,7 +1130,7 @@ static bool tail_setup(cmbs *s, int fast_only) {
         for (int k = 0; k < 2; k++) {
             const size_t b = bytes[k == s->tail_qf ? 0 : 1];
             s->tail_S[p][k].alloc(b);
-            HIP_CHECK(hipMemset(s->tail_S[p][k].p, 0, b));   // padding rows / columns stay 0
+            HIP_CHECK(hipMemset(s->tail_S[p][k].p, 0, b));   // padding bins / walkers stay 0
         }
     std::vector<unsigned char> rc((size_t)rows + 16, 0);
     for (const WinCol &c : s->tp_stage[s->tail_g].cols) rc[c.row] = c.cal ? 1 : 0;
@@ -1179,6 +1179,7 @@ static StepTail make_tail(cmbs *s, int rd, int wr) {
         t.q.ld_nuis = std::max(1, Q.n_nuis);
         t.q.cal_index = s->tp_stage[s->tail_qf].cal_index;
         t.q.W = W;
+        t.q.Wp = QuadForm::wpad(W);
         t.nq = t.q.src.n_items * (QuadForm::wpad(W) / QF_TILE);
         if (!G.corun_small(t.g, W, s->dc.like_nuis[gi], G.n_nuis, s->like_terms.as<double>() + (size_t)gi * s->dc.ld,
                            s->like_ws[gi].p))
@@ -1200,8 +1201,9 @@ static StepTail make_tail(cmbs *s, int rd, int wr) {
             const int i = s->tp_like[k];
             const WinStage &st = s->tp_stage[k];
             Like &L = *s->likes[i].like->like;
-            o[k] = TPOut{st.kind, st.cal_index, st.ld, 0, s->tail_S[wr][k].as<double>(), st.X, s->dc.like_nuis[i],
-                         (long long)std::max(1, L.n_nuis)};
+            // (the raw pass stores the kind-1 stage bin-major, steptail.h: its row stride is wpad(W))
+            o[k] = TPOut{st.kind, st.cal_index, st.kind == 1 ? QuadForm::wpad(W) : st.ld, 0,
+                         s->tail_S[wr][k].as<double>(), st.X, s->dc.like_nuis[i], (long long)std::max(1, L.n_nuis)};
         }
         t.tp = s->tpass->dev_args(o, W);
         const TheoryView &P = s->likes[s->tp_like[0]].th;

@@ -21,13 +21,22 @@
 
 namespace cmamd {
 
+// The kind-1 stage's raw sums are stored bin-major, S[Np][Wp] with Wp =
+// QuadForm::wpad(W) (both halves of the sampler's tail_S): the pass's emit has
+// 16 consecutive walkers on a wave's lanes, so each of its store instructions
+// writes whole 128-byte lines (4 bins x 16 walkers) instead of 64 eight-byte
+// pieces of 64 walker rows, and the quadratic form's lanes, 16 walkers wide as
+// well, read whole lines too (qfs_body.h).  Only this buffer is bin-major: the
+// pass's calibrated Delta rows (quadform_corun, quadform_pair_ticket,
+// theory_window_vec / pair, dragging) stay walker-major [Wp][Np].
 struct QFSArgs {             // the quadratic form from raw sums (QFSource + the step's rows)
     QFSource src;
-    const double *S;         // [Wp][Np] raw bin sums (padding rows and columns zero)
+    const double *S;         // [Np][Wp] raw bin sums (padding bins and walkers >= W zero, never stored)
     const double *nuis;      // [W][ld_nuis] the walkers' step-k nuisance values
     long long ld_nuis;
     int cal_index;           // cal in nuis (-1: none)
     int W;
+    int Wp;                  // S's row stride, QuadForm::wpad(W)
 };
 
 struct StepTail {

@@ -32,7 +32,7 @@ struct TPOut {            // a stage's output for one launch
     int cal_index;        // calibration parameter index in nuis (-1: none)
     int ld;               // kind 1: row stride of out
     int pad;
-    double *out;          // kind 0: [row][W]; kind 1: [W][ld]
+    double *out;          // kind 0: [row][W]; kind 1: [W][ld], the raw pass's sums [row][ld] (steptail.h)
     const double *X;      // kind 1
     const double *nuis;   // [W][ld_nuis]
     long long ld_nuis;

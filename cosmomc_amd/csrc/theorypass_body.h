@@ -32,7 +32,8 @@ template <int NB> constexpr int tp_vec_lds_bytes() {
 //
 // RAW (the sampler's unified step launch, mh_step_kernel): no calibration at
 // all -- every column's sum v is stored as it comes out of the MFMAs, at the
-// index its stage's output would take (out is then the stage's raw-sum buffer);
+// index its stage's output would take, except that the kind-1 stage's buffer is
+// bin-major, [row][ld] (steptail.h) (out is then the stage's raw-sum buffer);
 // the consumers apply the calibrations of the step that reads them with the
 // emit's own operations (X - v / cal^2 in the quadratic form's operand, v /
 // cal^2 in the small chi^2's partial rows), so the results are the same bits.
@@ -183,8 +184,11 @@ __device__ __forceinline__ void tp_vec_body(const TPDev &c, const double *__rest
                 double *out = o1 ? c.out[1].out : c.out[0].out;
                 if ((o1 ? c.out[1].kind : c.out[0].kind) == 0)
                     out[(long long)d[r].row * W + w] = q;
+                else if (RAW)   // bin-major: the 16 walkers li of each of the 4 bins kq fill a 128-byte line
+                                // (plain stores: write-through ones measured slower)
+                    out[(long long)d[r].row * (o1 ? c.out[1].ld : c.out[0].ld) + w] = v;
                 else
-                    out[(long long)w * (o1 ? c.out[1].ld : c.out[0].ld) + d[r].row] = RAW ? v : x[r] - q;
+                    out[(long long)w * (o1 ? c.out[1].ld : c.out[0].ld) + d[r].row] = x[r] - q;
             }
         }
     };
