@@ -57,6 +57,11 @@ class CmbtDerivedConfig(C.Structure):
                 ("lo", C.POINTER(C.c_double)), ("hi", C.POINTER(C.c_double))]
 
 
+class CmbgConfig(C.Structure):
+    _fields_ = [("n", C.c_int), ("coef", C.POINTER(C.c_double)), ("obs", C.POINTER(C.c_double)),
+                ("invcov", C.POINTER(C.c_double))]
+
+
 _lib = None
 
 # cmbs_theory_fn: int (*)(void *user, int W, const double *P_end, long long ld, void *stream)
@@ -130,6 +135,12 @@ def lib():
         L.cmbt_derived_count.argtypes = [vp]
         L.cmbt_derived_eval.argtypes = [vp, i, vp, ll, i, vp, ll, vp, vp]
         L.cmbs_set_theory_calculator.argtypes = [vp, vp]
+        L.cmbg_create.argtypes = [vp, C.POINTER(CmbgConfig), C.POINTER(vp), C.c_char_p, sz]
+        L.cmbg_destroy.argtypes = [vp]
+        L.cmbg_last_error.argtypes = [vp]
+        L.cmbg_last_error.restype = C.c_char_p
+        L.cmbg_eval.argtypes = [vp, i, vp, ll, i, vp, vp, vp]
+        L.cmbs_add_derived_likelihood.argtypes = [vp, vp]
         L.cmbs_collector_enable.argtypes = [vp, i]
         L.cmbs_collector_add.argtypes = [vp, vp, i, i, i, vp]
         L.cmbs_collector_state_host.argtypes = [vp, vp, vp, vp, vp]
@@ -167,7 +178,8 @@ def check(rc: int, handle=None, kind: str = "cmbl"):
     if rc != 0:
         msg = ""
         if handle is not None:
-            fn = {"cmbl": lib().cmbl_last_error, "cmbs": lib().cmbs_last_error, "cmbt": lib().cmbt_last_error}[kind]
+            fn = {"cmbl": lib().cmbl_last_error, "cmbs": lib().cmbs_last_error, "cmbt": lib().cmbt_last_error,
+                  "cmbg": lib().cmbg_last_error}[kind]
             msg = (fn(handle) or b"").decode()
         raise NativeError(rc, msg)
 

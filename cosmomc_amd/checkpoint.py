@@ -52,8 +52,11 @@ def write_checkpoint(root: str, sampler, propose_cov, chains=None, exchange=None
         meta["history"] = {"first": first, "count": count - first, "capacity": sampler._hist_cap}
         if count > first:
             hist = np.ascontiguousarray(sampler.history_host(first, count - first)).tobytes()
-            if getattr(sampler, "_likes", None):
-                meta["history"]["terms"] = len(sampler._likes)
+            n_terms = getattr(sampler, "n_term_rows", None)         # data and derived likelihoods
+            if n_terms is None:
+                n_terms = len(getattr(sampler, "_likes", None) or [])
+            if n_terms:
+                meta["history"]["terms"] = n_terms
                 hist += np.ascontiguousarray(sampler.history_terms(first, count - first)).tobytes()
     js = json.dumps(meta).encode()
     tmp = root + ".chk_tmp"

@@ -418,6 +418,38 @@ int cmbt_derived_eval(cmbt_t *t, int M, const double *P, long long ld, int num_p
     });
 }
 
+int cmbg_create(cmbt_t *calc, const cmbg_config_t *cfg, cmbg_t **out, char *errbuf, size_t errlen) {
+    std::string err;
+    if (!calc || !cfg || !out) {
+        put_err(errbuf, errlen, "cmbg_create: null argument");
+        return CMBL_ERR_ARG;
+    }
+    *out = nullptr;
+    std::unique_ptr<cmbg> g(new cmbg);
+    int rc = guarded(&err, [&] { cmamd::theorygauss_create(g.get(), calc, cfg); });
+    if (rc) {
+        put_err(errbuf, errlen, err.c_str());
+        return rc;
+    }
+    *out = g.release();
+    return CMBL_OK;
+}
+
+void cmbg_destroy(cmbg_t *g) { delete g; }
+const char *cmbg_last_error(const cmbg_t *g) { return g ? g->last_error.c_str() : ""; }
+
+int cmbg_eval(cmbg_t *g, int M, const double *P, long long ld, int num_params, double *out, int *fail, void *stream) {
+    if (!g) return CMBL_ERR_ARG;
+    return guarded(&g->last_error, [&] {
+        cmamd::theorygauss_eval(g, M, P, ld, num_params, out, fail, (hipStream_t)stream);
+    });
+}
+
+int cmbs_add_derived_likelihood(cmbs_t *s, cmbg_t *g) {
+    if (!s) return CMBL_ERR_ARG;
+    return guarded(&s->last_error, [&] { cmamd::sampler_add_derived_likelihood(s, g); });
+}
+
 int cmbs_set_theory_calculator(cmbs_t *s, cmbt_t *calc) {
     if (!s) return CMBL_ERR_ARG;
     return guarded(&s->last_error, [&] { cmamd::sampler_set_theory_calculator(s, calc); });

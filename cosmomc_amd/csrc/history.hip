@@ -143,8 +143,8 @@ void sampler_enable_history(cmbs *s, int capacity) {
     s->hist.alloc((size_t)capacity * (s->n_used + 1) * s->W * 8);   // per step: P(params_used) rows, CurLike row
     s->hist_cap = capacity;
     s->hist_count = 0;
-    if (!s->likes.empty()) {   // per step: each likelihood's -lnL at the current point
-        s->hist_terms.alloc((size_t)capacity * s->likes.size() * s->W * 8);
+    if (s->n_rows() > 0) {   // per step: each likelihood's -lnL at the current point
+        s->hist_terms.alloc((size_t)capacity * s->n_rows() * s->W * 8);
         HIP_CHECK(hipMemset(s->hist_terms.p, 0, s->hist_terms.bytes));
     }
 }
@@ -196,7 +196,7 @@ void sampler_history_terms_host(cmbs *s, int first, int count, double *out) {
     const int oldest = std::max(0, s->hist_count - s->hist_cap);
     if (first < oldest || first + count > s->hist_count)
         fail(CMBL_ERR_ARG, "history rows [%d, %d) not kept (rows %d..%d)", first, first + count, oldest, s->hist_count - 1);
-    const size_t blk = s->likes.size() * (size_t)s->W;
+    const size_t blk = (size_t)s->n_rows() * s->W;
     if (blk == 0) return;
     HIP_CHECK(hipDeviceSynchronize());
     for (int k = 0; k < count; k++) {
@@ -222,7 +222,7 @@ void sampler_history_restore(cmbs *s, int first, int count, const double *in, co
         HIP_CHECK(hipMemcpy(s->hist.as<double>() + (size_t)slot * blk, in + (size_t)k * blk, blk * 8,
                             hipMemcpyHostToDevice));
     }
-    const size_t tblk = s->likes.size() * (size_t)s->W;
+    const size_t tblk = (size_t)s->n_rows() * s->W;
     if (terms && tblk)
         for (int k = 0; k < count; k++) {
             const int slot = (first + k) % s->hist_cap;

@@ -165,6 +165,8 @@ struct LikeSlot {
 
 }  // namespace cmamd
 
+struct cmbg;
+
 struct cmbs {
     cmamd::DevCfg dc{};
     int W = 0, np = 0, n_used = 0;
@@ -181,6 +183,16 @@ struct cmbs {
     std::vector<int> h_tab_i;
     std::vector<double> h_tab_d;
     std::vector<cmamd::LikeSlot> likes;
+    // derived likelihoods (cmbs_add_derived_likelihood; not owned): Gaussian terms
+    // on surfaces of the theory calculator.  Their term rows follow the data
+    // likelihoods' in like_terms, cur_terms, like_terms2, the history terms and
+    // the state image (DevCfg::n_like counts both), with no DataParams and no
+    // dependent parameters.  Only slow evaluations (cmbs_set_start, slow steps)
+    // compute them; a fast step's trial keeps the current term, so its rows of
+    // like_terms must hold the current terms then (drv_cur: they do)
+    std::vector<cmbg *> dlikes;
+    bool drv_cur = false;
+    int n_rows() const { return (int)(likes.size() + dlikes.size()); }
     // host copies of the proposer structure
     std::vector<int> indices, proposer_for_index, blk_start, blk_n, blk_nchanged, used_params_changed_all;
     std::vector<int> blk_changed_off, blk_map_off, blk_R_off, changed;
@@ -296,6 +308,7 @@ void sampler_step_drag(cmbs *s, int n_steps, double dragging_steps, cmbs_theory_
 void sampler_step_theory(cmbs *s, int n_steps, cmbs_theory_fn fn, void *user, hipStream_t stream);
 void sampler_refresh_theory(cmbs *s, cmbs_theory_fn fn, void *user, hipStream_t stream);
 void sampler_set_theory_calculator(cmbs *s, cmbt *calc);
+void sampler_add_derived_likelihood(cmbs *s, cmbg *g);
 void sampler_collector_enable(cmbs *s, int samp_capacity);
 void sampler_collector_add(cmbs *s, const int *steps, int nsteps, int min_update, int check_burn, hipStream_t st);
 void sampler_collector_state_host(cmbs *s, int *start, int *count, int *burn, int *thin);

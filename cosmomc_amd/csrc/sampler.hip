@@ -715,6 +715,32 @@ static void setup_fusion(cmbs *s) {
         }
 }
 
+// One more term row (a likelihood was pushed): like_terms, cur_terms and the
+// history's terms ring grow, the existing rows kept
+static void add_term_row(cmbs *s) {
+    const int rows = s->n_rows(), li = rows - 1;
+    const size_t nlk = ((size_t)rows + 1) & ~size_t(1);
+    DevBuf nt(nlk * (size_t)s->dc.ld * 8);
+    HIP_CHECK(hipMemset(nt.p, 0, nt.bytes));
+    if (li > 0) HIP_CHECK(hipMemcpy(nt.p, s->like_terms.p, (size_t)li * s->dc.ld * 8, hipMemcpyDeviceToDevice));
+    std::swap(nt.p, s->like_terms.p);
+    std::swap(nt.bytes, s->like_terms.bytes);
+    s->dc.n_like = rows;
+    s->dc.like_terms = s->like_terms.as<double>();
+    {   // current-point terms: one more row, the existing ones kept
+        DevBuf ct((size_t)rows * s->dc.ld * 8);
+        HIP_CHECK(hipMemset(ct.p, 0, ct.bytes));
+        if (li > 0) HIP_CHECK(hipMemcpy(ct.p, s->cur_terms.p, (size_t)li * s->dc.ld * 8, hipMemcpyDeviceToDevice));
+        std::swap(ct.p, s->cur_terms.p);
+        std::swap(ct.bytes, s->cur_terms.bytes);
+        s->dc.cur_terms = s->cur_terms.as<double>();
+    }
+    if (s->hist_cap > 0) {   // the terms ring follows the number of likelihoods
+        s->hist_terms.alloc((size_t)s->hist_cap * rows * s->W * 8);
+        HIP_CHECK(hipMemset(s->hist_terms.p, 0, s->hist_terms.bytes));
+    }
+}
+
 void sampler_add_likelihood(cmbs *s, cmbl_t *like, const int *nuisance_indices, const double *dl, long long ld_field,
                             long long ld_walker) {
     if (!like) fail(CMBL_ERR_ARG, "null likelihood");
@@ -726,6 +752,8 @@ void sampler_add_likelihood(cmbs *s, cmbl_t *like, const int *nuisance_indices, 
             fail(CMBL_ERR_ARG, "nuisance index %d out of range 1..%d", nuisance_indices[q], s->np);
         nidx[q] = nuisance_indices[q] - 1;
     }
+    if (!s->dlikes.empty())
+        fail(CMBL_ERR_ARG, "data likelihoods are added before derived likelihoods (their term rows come first)");
     if ((int)s->likes.size() >= MAXLIKE) fail(CMBL_ERR_ARG, "at most %d likelihoods per sampler", MAXLIKE);
     const int li = (int)s->likes.size();
     s->likes.push_back({like, nidx, TheoryView{dl, ld_field, ld_walker}});
@@ -735,26 +763,7 @@ void sampler_add_likelihood(cmbs *s, cmbl_t *like, const int *nuisance_indices, 
     s->dc.tl.n_int = (int)s->h_tab_i.size();
     set_mh_lds(s);
     upload_tables(s);
-    const size_t nlk = (s->likes.size() + 1) & ~size_t(1);
-    DevBuf nt(nlk * (size_t)s->dc.ld * 8);
-    HIP_CHECK(hipMemset(nt.p, 0, nt.bytes));
-    if (li > 0) HIP_CHECK(hipMemcpy(nt.p, s->like_terms.p, (size_t)li * s->dc.ld * 8, hipMemcpyDeviceToDevice));
-    std::swap(nt.p, s->like_terms.p);
-    std::swap(nt.bytes, s->like_terms.bytes);
-    s->dc.n_like = (int)s->likes.size();
-    s->dc.like_terms = s->like_terms.as<double>();
-    {   // current-point terms: one more row, the existing ones kept
-        DevBuf ct((size_t)s->likes.size() * s->dc.ld * 8);
-        HIP_CHECK(hipMemset(ct.p, 0, ct.bytes));
-        if (li > 0) HIP_CHECK(hipMemcpy(ct.p, s->cur_terms.p, (size_t)li * s->dc.ld * 8, hipMemcpyDeviceToDevice));
-        std::swap(ct.p, s->cur_terms.p);
-        std::swap(ct.bytes, s->cur_terms.bytes);
-        s->dc.cur_terms = s->cur_terms.as<double>();
-    }
-    if (s->hist_cap > 0) {   // the terms ring follows the number of likelihoods
-        s->hist_terms.alloc((size_t)s->hist_cap * s->likes.size() * s->W * 8);
-        HIP_CHECK(hipMemset(s->hist_terms.p, 0, s->hist_terms.bytes));
-    }
+    add_term_row(s);
     s->nuis_bufs[li].alloc((size_t)std::max(nn, 1) * s->W * 8);
     s->dc.like_nuis[li] = s->nuis_bufs[li].as<double>();
     s->dc.like_nn[li] = nn;
@@ -777,6 +786,55 @@ void sampler_add_likelihood(cmbs *s, cmbl_t *like, const int *nuisance_indices, 
     for (int i : s->tp_like)
         if (i >= 0 && !s->like_ws[i].p) s->like_ws[i].alloc(s->likes[i].like->like->workspace_size(s->W));
     if (s->n_groups > 1) sampler_set_groups(s, s->n_groups);   // resize the group workspaces
+}
+
+// A derived likelihood: one more term row after the data likelihoods', with no
+// DataParams and no dependent parameters.  The pipelined fast-step schedules
+// carry the data likelihoods' rows alone, so with a derived likelihood the
+// fast steps take the general schedule (the same bits).
+void sampler_add_derived_likelihood(cmbs *s, cmbg *g) {
+    if (!g) fail(CMBL_ERR_ARG, "null derived likelihood");
+    if (s->n_rows() >= MAXLIKE) fail(CMBL_ERR_ARG, "at most %d likelihoods per sampler", MAXLIKE);
+    const int r = s->n_rows();
+    s->dlikes.push_back(g);
+    add_term_row(s);
+    s->dc.like_nidx[r] = 0;
+    s->dc.like_nn[r] = 0;
+    s->dc.like_nuis[r] = nullptr;
+    set_change_mask(s);
+    s->drv_cur = false;
+    s->tail_ready = 0;
+    s->pipe_ready = 0;
+    s->drag_dd.release();   // the drag's scratch rows follow the number of term rows
+}
+
+// the derived likelihoods' term rows (of `terms` [n_like][ld]) at the
+// parameter rows Prows [np][ld]
+static void eval_derived_rows(cmbs *s, const double *Prows, double *terms, int *fail_flags, hipStream_t stream) {
+    for (size_t k = 0; k < s->dlikes.size(); k++)
+        theorygauss_eval(s->dlikes[k], s->W, Prows, (long long)s->dc.ld, s->np,
+                         terms + (s->likes.size() + k) * (size_t)s->dc.ld, k == 0 ? fail_flags : nullptr, stream);
+}
+
+// A fast step's trial has the walker's slow point, so its derived terms are the
+// current ones: the dense paths read every row from like_terms, whose derived
+// rows hold a slow trial's terms after a slow step
+static void derived_rows_current(cmbs *s, hipStream_t stream) {
+    if (s->dlikes.empty() || s->drv_cur) return;
+    const size_t off = s->likes.size() * (size_t)s->dc.ld;
+    HIP_CHECK(hipMemcpyAsync(s->like_terms.as<double>() + off, s->cur_terms.as<double>() + off,
+                             s->dlikes.size() * (size_t)s->dc.ld * 8, hipMemcpyDeviceToDevice, stream));
+    s->drv_cur = true;
+}
+
+// derived likelihoods are evaluated by the sampler's calculator
+static void check_derived_calc(const cmbs *s, const char *entry) {
+    if (s->dlikes.empty()) return;
+    if (!s->calc)
+        fail(CMBL_ERR_ARG, "%s: derived likelihoods need the theory calculator (cmbs_set_theory_calculator)", entry);
+    for (size_t k = 0; k < s->dlikes.size(); k++)
+        if (s->dlikes[k]->calc != s->calc)
+            fail(CMBL_ERR_ARG, "%s: derived likelihood %zu was created on another calculator than the sampler's", entry, k);
 }
 
 // Change mask set-up (recomputed as likelihoods are added).  dependent_params
@@ -804,9 +862,13 @@ static void set_change_mask(cmbs *s) {
         s->dc.like_out[li] = nullptr;
         if (maskable && s->likes[li].like->like->sparse_capable()) s->sparse_likes.push_back(li);
     }
+    for (int r = nl; r < s->n_rows(); r++) {   // derived likelihoods: a fast step's trial keeps their current term
+        s->dc.like_dep[r] = 0;
+        s->dc.like_out[r] = nullptr;
+    }
     s->mask_on = !s->sparse_likes.empty();
     if (!s->mask_on) return;
-    s->like_flag.alloc((size_t)nl * ld * 4);
+    s->like_flag.alloc((size_t)s->n_rows() * ld * 4);
     s->dc.like_flag = s->like_flag.as<int>();
     s->like_cnt.alloc(256);
     for (int li : s->sparse_likes) {
@@ -831,7 +893,7 @@ static HistRow next_hist(cmbs *s) {
     if (s->hist_cap == 0) return r;
     const size_t slot = (size_t)(s->hist_count % s->hist_cap);
     r.p = s->hist.as<double>() + slot * (s->n_used + 1) * s->W;
-    if (!s->likes.empty() && s->hist_terms.p) r.t = s->hist_terms.as<double>() + slot * s->likes.size() * s->W;
+    if (s->n_rows() > 0 && s->hist_terms.p) r.t = s->hist_terms.as<double>() + slot * s->n_rows() * s->W;
     s->hist_count++;
     return r;
 }
@@ -913,7 +975,7 @@ void sampler_check_pipe(cmbs *s, bool wait) {
 static bool bin_setup(cmbs *s, int fast_only, PlikBinArgs &pb) {
     // (mode 3 needs the fused pass, so it falls back here with plik_lite alone)
     if (s->pipe_mode == 0 || !fast_only || s->tpass || s->n_groups != 1 || s->mask_on ||
-        s->likes.size() != 1 || !is_deferred(s, 0))
+        s->likes.size() != 1 || !s->dlikes.empty() || !is_deferred(s, 0))
         return false;
     const LikeSlot &L = s->likes[0];
     WinStage st;
@@ -970,7 +1032,7 @@ static LeanCfg lean_cfg(const cmbs *s, int fast_only, bool masked) {
         return L;
     const int b = s->proposer_for_index[s->slow_n] - 1;
     if (s->blk_n[b] != 1 || s->blk_nchanged[b] > LEAN_MAXC || lean_lds_bytes(s) > s->mh_lds) return L;
-    for (int l = 0; l < d.n_like; l++) {
+    for (int l = 0; l < (int)s->likes.size(); l++) {   // (a derived likelihood's row has none)
         const std::vector<int> &ni = s->likes[l].nidx;
         if ((int)ni.size() > LEAN_MAXQ) return LeanCfg{};
         L.nn[l] = (int)ni.size();
@@ -1064,6 +1126,7 @@ static void launch_mh(cmbs *s, bool accept, bool propose, int fast_only, const H
 }
 
 void sampler_set_start(cmbs *s, const double *P0, hipStream_t stream) {
+    check_derived_calc(s, "cmbs_set_start");
     // host [W][np] -> device trial rows [np][W]
     std::vector<double> t((size_t)s->np * s->W);
     for (int w = 0; w < s->W; w++)
@@ -1074,6 +1137,8 @@ void sampler_set_start(cmbs *s, const double *P0, hipStream_t stream) {
     HIP_CHECK(hipStreamSynchronize(stream));
     gather_trial_nuis(s, stream);
     eval_likes(s, stream, 0, s->W, s->ws.p);
+    eval_derived_rows(s, s->dc.sd + (size_t)s->dc.rows.T * s->dc.ld, s->like_terms.as<double>(), nullptr, stream);
+    s->drv_cur = true;   // start_kernel makes these terms the current ones
     hipLaunchKernelGGL(start_kernel, dim3((s->W + 255) / 256), dim3(256), 0, stream, s->dc);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(stream));
@@ -1096,7 +1161,7 @@ static bool tail_setup(cmbs *s, int fast_only) {
     // run takes the unpipelined steps, whose eval_likes runs every likelihood; BASELINE
     // configs[2] with a lowl term would be such a run -- clik is absent, so none exists here)
     if (s->pipe_mode == 0 || !fast_only || !s->tpass || s->n_groups != 1 || s->mask_on ||
-        (s->dc.rot_defer && s->rot_fast_any) || s->likes.size() != 2)
+        (s->dc.rot_defer && s->rot_fast_any) || s->likes.size() != 2 || !s->dlikes.empty())
         return false;
     {
         const TheoryView &P = s->likes[s->tp_like[0]].th;
@@ -1297,9 +1362,11 @@ void sampler_step(cmbs *s, int n_steps, int fast_only, hipStream_t stream) {
     if (!s->started) fail(CMBL_ERR_ARG, "cmbs_set_start must be called before cmbs_step");
     check_theory_fresh(s);
     if (fast_only && s->fast_n == 0) fail(CMBL_ERR_ARG, "no fast parameters");
-    if (!fast_only && s->slow_n > 0 && !s->likes.empty())
+    if (!fast_only && s->slow_n > 0 && s->n_rows() > 0)
         fail(CMBL_ERR_ARG, "slow proposals need the theory at the trial point: use cmbs_step_theory");
+    check_derived_calc(s, "cmbs_step");
     if (n_steps <= 0) return;
+    derived_rows_current(s, stream);
     // propose(1) | likes | accept(1)+propose(2) | likes | ... | likes | accept(n)
     const int G = s->n_groups;
     sampler_check_pipe(s);

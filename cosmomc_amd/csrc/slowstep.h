@@ -70,7 +70,7 @@ __global__ void calc_fail_terms(const int *__restrict__ flag, double *terms, int
 
 static void apply_calc_fail(cmbs *s, hipStream_t stream) {
     hipLaunchKernelGGL(calc_fail_terms, dim3((s->W + 255) / 256), dim3(256), 0, stream, s->calc_fail.as<int>(),
-                       s->like_terms.as<double>(), (int)s->likes.size(), s->W, (size_t)s->dc.ld);
+                       s->like_terms.as<double>(), s->n_rows(), s->W, (size_t)s->dc.ld);
     HIP_CHECK(hipGetLastError());
 }
 
@@ -88,6 +88,25 @@ static void check_slow_entry(const cmbs *s, const char *entry, cmbs_theory_fn fn
             fail(CMBL_ERR_ARG, "%s: likelihood %zu needs per-walker theory rows (ld_walker > 0)", entry, i);
     }
     if (!fn && !s->calc) fail(CMBL_ERR_ARG, "%s needs a theory function or a theory calculator", entry);
+    check_derived_calc(s, entry);
+}
+
+// The term rows of a slow step's end points Prows (the trial rows): the data
+// likelihoods on the trial theories (`pair`: a drag's, by the paired launches
+// when they apply), then the derived likelihoods from the calculator.  With the
+// calculator as the theory source a point outside its box or a hard range gets
+// logZero in every row; a callback step ignores the D_l failure flags, and a
+// derived row is logZero outside the box by cmbg_eval's own rule.
+static void eval_end_rows(cmbs *s, cmbs_theory_fn fn, void *user, const double *Prows, bool pair, hipStream_t stream) {
+    const bool calc = fill_trial_theory(s, fn, user, Prows, stream);
+    if (!s->likes.empty() && !(pair && eval_likes_drag_pair(s, stream, false))) eval_likes_drag(s, end_set(s), stream);
+    // with no data likelihood no D_l launch has written the flags: the first
+    // derived row's box flags, and the calculator's range test over them
+    const bool own_flags = calc && s->likes.empty();
+    eval_derived_rows(s, Prows, s->like_terms.as<double>(), own_flags ? s->calc_fail.as<int>() : nullptr, stream);
+    if (!s->dlikes.empty()) s->drv_cur = false;
+    if (own_flags) theorycalc_range_flags(s->calc, s->W, Prows, (long long)s->dc.ld, s->calc_fail.as<int>(), stream);
+    if (calc) apply_calc_fail(s, stream);
 }
 
 // drag_staged_kernel's LDS image (0 when it would not fit a CU's 160 KB)
@@ -130,8 +149,8 @@ void sampler_step_drag(cmbs *s, int n_steps, double dragging_steps, cmbs_theory_
                        hipStream_t stream) {
     rot_schedule_unknown(s);           // the drag proposals move the blocks' loop indices
     const bool drag = s->fast_n != 0 && s->slow_n != 0;   // else MCMC.f90:351-354: plain Metropolis
-    const int nl = (int)s->likes.size();
-    check_slow_entry(s, "cmbs_step_drag", fn, n_steps > 0 && drag && nl > 0);
+    const int nl = (int)s->likes.size(), nr = s->n_rows();
+    check_slow_entry(s, "cmbs_step_drag", fn, n_steps > 0 && drag && nr > 0);
     check_theory_fresh(s);
     if (n_steps <= 0) return;
     if (!drag) {
@@ -140,11 +159,11 @@ void sampler_step_drag(cmbs *s, int n_steps, double dragging_steps, cmbs_theory_
     }
     const size_t ld = s->dc.ld;
     if (!s->drag_dd.p) {
-        s->drag_dd.alloc((size_t)(3 * s->np + 4 + s->dc.max_blk + std::max<size_t>(1, s->likes.size())) * ld * 8);
+        s->drag_dd.alloc((size_t)(3 * s->np + 4 + s->dc.max_blk + std::max(1, nr)) * ld * 8);
         s->drag_di.alloc((size_t)(1 + s->all_n) * ld * 4);
         HIP_CHECK(hipMemset(s->drag_dd.p, 0, s->drag_dd.bytes));
         HIP_CHECK(hipMemset(s->drag_di.p, 0, s->drag_di.bytes));
-        s->like_terms2.alloc(std::max<size_t>(1, s->likes.size()) * ld * 8);
+        s->like_terms2.alloc((size_t)std::max(1, nr) * ld * 8);
         HIP_CHECK(hipMemset(s->like_terms2.p, 0, s->like_terms2.bytes));
         for (int i = 0; i < nl; i++)
             s->nuis_bufs2[i].alloc((size_t)std::max(s->likes[i].like->like->n_nuis, 1) * s->W * 8);
@@ -165,6 +184,7 @@ void sampler_step_drag(cmbs *s, int n_steps, double dragging_steps, cmbs_theory_
     for (int step = 0; step < n_steps; step++) {
         s->num_drag++;
         if (s->num_drag % s->dc.oversample_fast != 0) {   // FastParameterSample (:357-361)
+            derived_rows_current(s, stream);
             launch_mh(s, false, true, 1, HistRow{}, stream, 0, s->W, s->mask_on);
             eval_trial_likes(s, stream, false);
             launch_mh(s, true, false, 1, next_hist(s), stream, 0, s->W, s->mask_on);
@@ -172,10 +192,13 @@ void sampler_step_drag(cmbs *s, int n_steps, double dragging_steps, cmbs_theory_
         }
         g.istep = 0;
         launch_drag<0>(s, g, HistRow{}, stream);
-        if (nl > 0) {
-            const bool calc = fill_trial_theory(s, fn, user, s->dc.sd + (size_t)s->dc.rows.T * ld, stream);
-            if (!eval_likes_drag_pair(s, stream, false)) eval_likes_drag(s, end_set(s), stream);
-            if (calc) apply_calc_fail(s, stream);   // a flagged end point aborts its drag in stage 1
+        if (nr > 0) {   // (a flagged end point aborts its drag in stage 1)
+            eval_end_rows(s, fn, user, s->dc.sd + (size_t)s->dc.rows.T * ld, true, stream);
+            // the slow point of a drag's start does not move: its derived terms are the walker's current ones
+            if (nr > nl)
+                HIP_CHECK(hipMemcpyAsync(s->like_terms2.as<double>() + (size_t)nl * ld,
+                                         s->cur_terms.as<double>() + (size_t)nl * ld, (size_t)(nr - nl) * ld * 8,
+                                         hipMemcpyDeviceToDevice, stream));
         }
         launch_drag<1>(s, g, HistRow{}, stream);
         for (int is = 1; is <= interp - 1; is++) {
@@ -208,10 +231,10 @@ static void swap_accepted_theory(cmbs *s, hipStream_t stream) {
 }
 
 void sampler_step_theory(cmbs *s, int n_steps, cmbs_theory_fn fn, void *user, hipStream_t stream) {
-    check_slow_entry(s, "cmbs_step_theory", fn, n_steps > 0 && !s->likes.empty());
+    check_slow_entry(s, "cmbs_step_theory", fn, n_steps > 0 && s->n_rows() > 0);
     check_theory_fresh(s);
     if (n_steps <= 0) return;
-    if (s->likes.empty()) {
+    if (s->n_rows() == 0) {
         sampler_step(s, n_steps, 0, stream);
         return;
     }
@@ -220,9 +243,7 @@ void sampler_step_theory(cmbs *s, int n_steps, cmbs_theory_fn fn, void *user, hi
         launch_mh(s, k > 0, k < n_steps, 0, k > 0 ? next_hist(s) : HistRow{}, stream, 0, s->W);
         if (k > 0) swap_accepted_theory(s, stream);
         if (k == n_steps) break;
-        const bool calc = fill_trial_theory(s, fn, user, s->dc.sd + (size_t)s->dc.rows.T * s->dc.ld, stream);
-        eval_likes_drag(s, end_set(s), stream);
-        if (calc) apply_calc_fail(s, stream);
+        eval_end_rows(s, fn, user, s->dc.sd + (size_t)s->dc.rows.T * s->dc.ld, false, stream);
     }
 }
 

@@ -31,7 +31,7 @@ void sampler_get_state_host(cmbs *s, double *P, double *cur_like, double *mult, 
 // table and Gaussian1 cache, cyclic-index and rotation state, each
 // likelihood's term at the point -- so a resumed run continues each chain
 // exactly.  Layout: StateHeader, double rows [ND][W], int rows [NI][W],
-// current terms [n_like][W].  The proposal covariance is the caller's part
+// current terms [n_like][W] (data then derived likelihoods).  The proposal covariance is the caller's part
 // (cmbs_set_covariance before cmbs_load_state).
 struct StateHeader {
     unsigned magic, version;
@@ -43,14 +43,14 @@ static constexpr unsigned STATE_MAGIC = 0x53424d43u;   // "CMBS"
 
 size_t sampler_state_bytes(const cmbs *s) {
     const Rows &R = s->dc.rows;
-    return sizeof(StateHeader) + (size_t)(R.ND + s->likes.size()) * s->W * 8 + (size_t)R.NI * s->W * 4 +
+    return sizeof(StateHeader) + (size_t)(R.ND + s->n_rows()) * s->W * 8 + (size_t)R.NI * s->W * 4 +
            sampler_collector_bytes(s);
 }
 
 static StateHeader state_header(const cmbs *s) {
     const Rows &R = s->dc.rows;
     return StateHeader{STATE_MAGIC, 2u, s->W, s->np, s->n_used, s->nblocks, s->all_n, s->slow_n, s->fast_n,
-                       s->R_total, R.ND, R.NI, (int)s->likes.size(), s->theory_moved ? 1 : 0,
+                       s->R_total, R.ND, R.NI, s->n_rows(), s->theory_moved ? 1 : 0,
                        s->coll.enabled ? s->coll.cap : 0, 0, s->num_drag};
 }
 
@@ -69,9 +69,9 @@ void sampler_save_state(cmbs *s, void *buf, size_t bytes) {
     p += (size_t)R.ND * W * 8;
     HIP_CHECK(hipMemcpy2D(p, W * 4, s->dc.si, ld * 4, W * 4, R.NI, hipMemcpyDeviceToHost));
     p += (size_t)R.NI * W * 4;
-    if (!s->likes.empty())
-        HIP_CHECK(hipMemcpy2D(p, W * 8, s->dc.cur_terms, ld * 8, W * 8, s->likes.size(), hipMemcpyDeviceToHost));
-    p += s->likes.size() * W * 8;
+    if (s->n_rows() > 0)
+        HIP_CHECK(hipMemcpy2D(p, W * 8, s->dc.cur_terms, ld * 8, W * 8, s->n_rows(), hipMemcpyDeviceToHost));
+    p += (size_t)s->n_rows() * W * 8;
     if (s->coll.enabled) sampler_collector_save(s, p);
 }
 
@@ -97,9 +97,10 @@ void sampler_load_state(cmbs *s, const void *buf, size_t bytes) {
     p += (size_t)R.ND * W * 8;
     HIP_CHECK(hipMemcpy2D(s->dc.si, ld * 4, p, W * 4, W * 4, R.NI, hipMemcpyHostToDevice));
     p += (size_t)R.NI * W * 4;
-    if (!s->likes.empty())
-        HIP_CHECK(hipMemcpy2D(s->dc.cur_terms, ld * 8, p, W * 8, W * 8, s->likes.size(), hipMemcpyHostToDevice));
-    p += s->likes.size() * W * 8;
+    if (s->n_rows() > 0)
+        HIP_CHECK(hipMemcpy2D(s->dc.cur_terms, ld * 8, p, W * 8, W * 8, s->n_rows(), hipMemcpyHostToDevice));
+    p += (size_t)s->n_rows() * W * 8;
+    s->drv_cur = false;   // the derived rows of like_terms are not part of the image
     if (s->coll.enabled) sampler_collector_load(s, p);
     s->num_drag = h.num_drag;
     s->theory_moved = h.theory_moved != 0;

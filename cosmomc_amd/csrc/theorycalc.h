@@ -6,6 +6,8 @@
 // logZero, calclike.f90:308-313).  Its derived outputs are the
 // parameterization's derived parameters and, with ranges, the hard cuts of
 // TP_NonBaseParameterPriors (CosmologyParameterizations.f90:90-112, 189-272).
+// A Gaussian likelihood on such surfaces (cmbg_*) is its Gaussian priors
+// (:105-110) and the Gaussian BAO likelihood (bao.f90:265-308).
 #pragma once
 
 #include <string>
@@ -40,10 +42,25 @@ struct cmbt {
     cmamd::DevBuf dcoef, dlim;
 };
 
+// Gaussian likelihood on derived quantities (cmbg_*): n scalar surfaces over
+// the calculator's monomials with coefficient columns of its own
+struct cmbg {
+    cmbt *calc = nullptr;         // not owned
+    int n = 0;
+    std::string last_error;
+    // device tables: dcoef [Kp][TD_ND] as cmbt's, obs [TD_ND] (padded with
+    // zeros), invcov [n][n]
+    cmamd::DevBuf dcoef, obs, invcov;
+};
+
 namespace cmamd {
+void theorygauss_create(cmbg *g, cmbt *calc, const cmbg_config_t *cfg);
+void theorygauss_eval(cmbg *g, int M, const double *P, long long ld, int num_params, double *out, int *fail_flags,
+                      hipStream_t stream);
 void theorycalc_create(cmbt *t, const cmbt_config_t *cfg);
 void theorycalc_eval(cmbt *t, int W, const double *P, long long ld, int num_params, double *dl, long long ld_field,
                      long long ld_walker, int *fail_flags, hipStream_t stream);
+void theorycalc_range_flags(cmbt *t, int W, const double *P, long long ld, int *fail_flags, hipStream_t stream);
 void theorycalc_set_derived(cmbt *t, const cmbt_derived_config_t *cfg);
 void theorycalc_derived_eval(cmbt *t, int M, const double *P, long long ld, int num_params, double *out,
                              long long ld_out, int *fail_flags, hipStream_t stream);

@@ -14,7 +14,11 @@
 // Derived parameters (cmbt_set_derived / cmbt_derived_eval): up to 32 scalar
 // surfaces over the same monomials, summed by the same chain, in a kernel of
 // their own (theory_derived_kernel) tiled for few outputs and many points.
+//
+// Gaussian likelihoods on such surfaces (cmbg_*, theory_gauss_kernel): the
+// same accumulators, then (v - obs)^T invcov (v - obs) / 2 per point.
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <limits>
 
@@ -49,6 +53,16 @@ struct TheoryDerivedArgs {
     int nd;
     double *out;                         // [nd][ld_out]; null: the flags only
     long long ld_out;
+    int *fail;
+};
+
+struct TheoryGaussArgs {
+    TheoryBasisArgs b;
+    const double *dcoef;                 // [Kp][TD_ND]
+    const double *obs;                   // [TD_ND]
+    const double *invcov;                // [n][n]
+    int n;
+    double *out;                         // [M]
     int *fail;
 };
 
@@ -239,6 +253,54 @@ __global__ __launch_bounds__(TD_THREADS) void theory_derived_kernel(TheoryDerive
     if (a.fail) a.fail[m] = bad | out_of_range;
 }
 
+// Gaussian likelihood on derived quantities: out[m] = (v - obs)^T invcov
+// (v - obs) / 2 with v the n surfaces of theory_derived_kernel (the same
+// accumulator groups, so v_i has its bits).  A thread owns one point.  Its
+// residuals r_i = v_i - obs_i go to an LDS column of its own ([n][TD_TM],
+// consecutive threads in consecutive doubles: no bank conflict), which lies
+// over the scaled inputs: with a point per thread tc_basis_tile reads and
+// writes only the thread's own column of them, and is done with it.  The
+// quadratic form's loops then run over LDS addresses, not over a register
+// array; obs and invcov are uniform and come by scalar loads.
+//   y_i = fma(invcov[i][j], r_j, y_i), j ascending from +0.0
+//   s   = fma(r_i, y_i, s),            i ascending from +0.0;   out = s / 2
+// A point outside the box gets logZero.
+__global__ __launch_bounds__(TD_THREADS) void theory_gauss_kernel(TheoryGaussArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];   // [max(n_in, n)][TD_TM]
+    const int m = blockIdx.x * TD_TM + threadIdx.x;
+    const int n = a.n, ng = (n + 7) >> 3;
+    const double *__restrict__ dcoef = a.dcoef;
+    double acc[TD_ND];
+#pragma unroll
+    for (int d = 0; d < TD_ND; d++) acc[d] = 0.0;
+#define TD_GROUP(g)                                                                              \
+    _Pragma("unroll") for (int q = 8 * (g); q < 8 * (g) + 8; q++) acc[q] = __builtin_fma(b, c[q], acc[q]);
+    const int bad = tc_basis_tile<TD_TM, TD_THREADS>(a.b, blockIdx.x * TD_TM, lds, [&](int k, int, double b) {
+        const double *__restrict__ c = dcoef + (size_t)k * TD_ND;
+        TD_GROUP(0)
+        if (ng > 1) { TD_GROUP(1) }
+        if (ng > 2) { TD_GROUP(2) }
+        if (ng > 3) { TD_GROUP(3) }
+    });
+#undef TD_GROUP
+    double *r = lds + threadIdx.x;
+    const double *__restrict__ obs = a.obs;
+#pragma unroll
+    for (int d = 0; d < TD_ND; d++)
+        if (d < n) r[d * TD_TM] = acc[d] - obs[d];
+    const double *__restrict__ ic = a.invcov;
+    double s = 0.0;
+    for (int i = 0; i < n; i++) {
+        double y = 0.0;
+        for (int j = 0; j < n; j++) y = __builtin_fma(ic[i * n + j], r[j * TD_TM], y);
+        s = __builtin_fma(r[i * TD_TM], y, s);
+    }
+    if (m >= a.b.W) return;
+    a.out[m] = bad ? CMBL_LOGZERO : s / 2;
+    if (a.fail) a.fail[m] = bad;
+}
+
 static size_t tc_lds_bytes(int Kp) { return ((size_t)Kp * TC_TW + (size_t)TC_KC * TC_TN) * 8; }
 static size_t td_lds_bytes(int n_in) { return (size_t)n_in * TD_TM * 8; }
 
@@ -366,6 +428,12 @@ void theorycalc_eval(cmbt *t, int W, const double *P, long long ld, int num_para
     if (t->ranged && fail_flags) launch_derived(t, W, P, ld, nullptr, 0, fail_flags, stream);
 }
 
+// With ranges set: box-or-range over the box flags of points that no
+// theorycalc_eval has flagged (a sampler with derived likelihoods alone)
+void theorycalc_range_flags(cmbt *t, int W, const double *P, long long ld, int *fail_flags, hipStream_t stream) {
+    if (t->ranged) launch_derived(t, W, P, ld, nullptr, 0, fail_flags, stream);
+}
+
 void theorycalc_set_derived(cmbt *t, const cmbt_derived_config_t *c) {
     if (!c) {
         t->n_derived = 0;
@@ -405,6 +473,54 @@ void theorycalc_derived_eval(cmbt *t, int M, const double *P, long long ld, int 
     for (int p : t->pidx)
         if (p > num_params) fail(CMBL_ERR_ARG, "cmbt_derived_eval: param_index %d outside 1..%d", p, num_params);
     launch_derived(t, M, P, ld, out, ld_out, fail_flags, stream);
+}
+
+void theorygauss_create(cmbg *g, cmbt *calc, const cmbg_config_t *c) {
+    if (c->n < 1 || c->n > CMBG_MAXN) fail(CMBL_ERR_ARG, "cmbg_create: n must be in 1..%d", CMBG_MAXN);
+    if (!c->coef || !c->obs || !c->invcov) fail(CMBL_ERR_ARG, "cmbg_create: null table");
+    const int n = c->n;
+    for (int i = 0; i < n; i++) {
+        if (!std::isfinite(c->obs[i])) fail(CMBL_ERR_ARG, "cmbg_create: obs %d is not finite", i);
+        for (int j = 0; j < n; j++) {
+            if (!std::isfinite(c->invcov[i * n + j])) fail(CMBL_ERR_ARG, "cmbg_create: invcov %d, %d is not finite", i, j);
+            if (c->invcov[i * n + j] != c->invcov[j * n + i])
+                fail(CMBL_ERR_ARG, "cmbg_create: invcov is not symmetric at %d, %d", i, j);
+        }
+    }
+    static_assert(CMBG_MAXN == TD_ND, "the accumulator groups of theory_derived_kernel");
+    std::vector<double> coef((size_t)calc->Kp * TD_ND, 0.0), obs(TD_ND, 0.0);
+    for (int k = 0; k < calc->K; k++)
+        std::copy(c->coef + (size_t)k * n, c->coef + (size_t)(k + 1) * n, coef.begin() + (size_t)k * TD_ND);
+    std::copy(c->obs, c->obs + n, obs.begin());
+    g->calc = calc;
+    g->n = n;
+    upload(g->dcoef, coef);
+    upload(g->obs, obs);
+    upload(g->invcov, std::vector<double>(c->invcov, c->invcov + (size_t)n * n));
+}
+
+void theorygauss_eval(cmbg *g, int M, const double *P, long long ld, int num_params, double *out, int *fail_flags,
+                      hipStream_t stream) {
+    cmbt *t = g->calc;
+    if (M <= 0 || M > std::numeric_limits<int>::max() - TD_TM)
+        fail(CMBL_ERR_ARG, "cmbg_eval: M must be in 1..%d", std::numeric_limits<int>::max() - TD_TM);
+    if (!P || !out) fail(CMBL_ERR_ARG, "cmbg_eval: null buffer");
+    if (ld < M) fail(CMBL_ERR_ARG, "cmbg_eval: ld %lld below M %d", ld, M);
+    for (int p : t->pidx)
+        if (p > num_params) fail(CMBL_ERR_ARG, "cmbg_eval: param_index %d outside 1..%d", p, num_params);
+    TheoryGaussArgs a{};
+    a.b = basis_args(t, M, P, ld);
+    a.dcoef = g->dcoef.as<double>();
+    a.obs = g->obs.as<double>();
+    a.invcov = g->invcov.as<double>();
+    a.n = g->n;
+    a.out = out;
+    a.fail = fail_flags;
+    timed_launch("theory_gauss_kernel", stream, [&](hipEvent_t e0, hipEvent_t e1) {
+        hipExtLaunchKernelGGL(theory_gauss_kernel, dim3((M + TD_TM - 1) / TD_TM), dim3(TD_THREADS),
+                              td_lds_bytes(std::max(t->n_in, g->n)), stream, e0, e1, 0, a);
+    });
+    HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace cmamd

@@ -141,7 +141,11 @@ class GPUEvaluator:
     sampler: a BatchedMCMC (W walkers, temperature = redo_temp, bounds and
     priors of the new run) with the new likelihoods registered;
     theory_fn(P [W, num_params] numpy) fills the registered theory buffers
-    for the rows (None: every row is scored on the cached theory)."""
+    for the rows (None: every row is scored on the cached theory).
+    Derived likelihoods of the sampler (add_derived_likelihood: Gaussian
+    priors on derived quantities, BAO) need no theory buffer: cmbs_set_start
+    evaluates their rows at the points from the sampler's calculator, so their
+    terms are part of the returned -lnL."""
 
     def __init__(self, sampler, theory_fn=None):
         self.s = sampler

@@ -74,6 +74,12 @@ class BatchedMCMC:
             raise N.NativeError(rc, err.value.decode())
         self._h = h
         self._likes = []
+        self._dlikes = []
+
+    @property
+    def n_term_rows(self) -> int:
+        """Rows of the per-likelihood terms: data likelihoods, then derived ones."""
+        return len(self._likes) + len(self._dlikes)
 
     def _check(self, rc):
         N.check(rc, self._h, "cmbs")
@@ -94,6 +100,15 @@ class BatchedMCMC:
         self._likes.append((like, dl))
         self._check(N.lib().cmbs_add_likelihood(self._h, like.handle, idx.ctypes.data, dl.data_ptr(), dl.stride(1),
                                                 dl.stride(0)))
+
+    def add_derived_likelihood(self, g):
+        """g: cosmomc_amd.derivedlike.DerivedGaussian on the calculator given to
+        set_theory_calculator (cmbs_add_derived_likelihood): one more term row
+        after the data likelihoods', so every add_likelihood call comes first.
+        The row is evaluated at the start point and at every slow trial and
+        drag end; fast steps keep the current term."""
+        self._check(N.lib().cmbs_add_derived_likelihood(self._h, g.handle))
+        self._dlikes.append(g)                       # not owned by the library: keep it alive
 
     def set_start(self, P0, stream=None):
         p = np.ascontiguousarray(P0, dtype=np.float64).reshape(self.W, self.np)
@@ -198,9 +213,10 @@ class BatchedMCMC:
 
     def history_terms(self, first: int, count: int):
         """Each likelihood's -lnL at history rows [first, first+count) on the
-        host: [count, n_likelihoods, W] (add_likelihood order)."""
-        out = np.empty((count, len(self._likes), self.W))
-        if self._likes:
+        host: [count, n_likelihoods, W] (add_likelihood order, then
+        add_derived_likelihood order)."""
+        out = np.empty((count, self.n_term_rows, self.W))
+        if self.n_term_rows:
             self._check(N.lib().cmbs_history_terms_host(self._h, first, count, out.ctypes.data))
         return out
 

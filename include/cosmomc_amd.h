@@ -369,6 +369,64 @@ int  cmbt_derived_eval(cmbt_t *t, int M, const double *P, long long ld, int num_
  * resumed run sets it again). */
 int  cmbs_set_theory_calculator(cmbs_t *s, cmbt_t *calc);
 
+/* ------------------------------------------------------------------ */
+/* Gaussian likelihood on calculator-derived quantities: the reference's
+ * Gaussian priors on derived parameters (H0_prior, zre_prior,
+ * CosmologyParameterizations.f90:105-110) and its Gaussian background
+ * likelihoods (TBAOLikelihood, bao.f90:265-308: D_V/r_s, D_M/r_s, H r_s, A(z),
+ * f sigma8 at a dataset's redshifts), with the theory vector taken from n
+ * scalar response surfaces over a calculator's monomials.
+ *
+ *   v_i    = sum_k basis_k(m) * coef[k][i]   box test, clamp, monomials and fma
+ *            chain of cmbt_derived_eval: v_i has the bits cmbt_derived_eval
+ *            gives for the same column
+ *   r_i    = v_i - obs_i
+ *   y_i    = fma(invcov[i][j], r_j, y_i), j ascending from +0.0
+ *   s      = fma(r_i, y_i, s),            i ascending from +0.0
+ *   out[m] = s / 2
+ * A point outside the calculator's box (a NaN input included) has out[m] =
+ * CMBL_LOGZERO exactly.  A point's bits depend on neither M, its place in the
+ * batch nor ld. */
+#define CMBG_MAXN 32
+typedef struct cmbg cmbg_t;
+typedef struct {
+    int n;                    /* 1..CMBG_MAXN theory values */
+    const double *coef;       /* host [n_terms][n]: n scalar surfaces over the calculator's monomials
+                                 (what cmbt_set_derived takes) */
+    const double *obs;        /* n */
+    const double *invcov;     /* n x n row-major, symmetric bit for bit */
+} cmbg_config_t;
+/* Copies the tables: the object keeps coefficient columns of its own, apart
+ * from what cmbt_set_derived holds.  `calc` is not owned and must outlive the
+ * object.  CMBL_ERR_ARG for n outside 1..32, a NULL table, a non-finite obs or
+ * invcov entry, or invcov[i][j] != invcov[j][i]. */
+int  cmbg_create(cmbt_t *calc, const cmbg_config_t *cfg, cmbg_t **out, char *errbuf, size_t errlen);
+void cmbg_destroy(cmbg_t *g);
+const char *cmbg_last_error(const cmbg_t *g);
+/* One launch (theory_gauss_kernel), asynchronous on `stream`, for M points:
+ *   P     device rows [num_params][ld], point-minor, as for cmbt_eval
+ *   out   device [M]
+ *   fail  device int[M]: 1 for a point outside the box, else 0; or NULL
+ * Nothing outside out[0..M) and fail[0..M) is written.  CMBL_ERR_ARG for
+ * ld < M or a param_index outside 1..num_params. */
+int  cmbg_eval(cmbg_t *g, int M, const double *P, long long ld, int num_params,
+               double *out, int *fail, void *stream);
+/* The object as a likelihood of the sampler: one more term row after the data
+ * likelihoods' (cur terms, history terms, the chi2_* chain columns, the
+ * cmbs_save_state image, whose n_like counts both kinds), summed in
+ * target_like after the data terms and divided by the temperature, where the
+ * reference puts NonBaseParameterPriors and BAO (calclike.f90:300).  In call
+ * order, at most 8 rows with the data likelihoods, whose cmbs_add_likelihood
+ * calls all come first.  The rows are evaluated with cmbg_eval at the start
+ * point and at the trial / drag-end rows of cmbs_step_theory and
+ * cmbs_step_drag (also with a theory_fn: the derived rows still come from the
+ * calculator); a fast step's trial keeps the walker's current term.  A
+ * sampler with derived likelihoods alone steps with cmbs_step_theory /
+ * cmbs_step_drag and needs no trial-theory buffer.  cmbs_set_theory_calculator
+ * must be set to the calculator the objects were created on: otherwise
+ * cmbs_set_start and the stepping entries return CMBL_ERR_ARG.  Not owned. */
+int  cmbs_add_derived_likelihood(cmbs_t *s, cmbg_t *g);
+
 /* Execution tuning (no reference counterpart; results are unchanged): split the
  * walkers into n_groups 64-aligned slices, each stepped on an internal stream
  * forked from / joined to the caller's, so the Metropolis kernel of one slice
