@@ -99,11 +99,13 @@ def lib():
         L.cmbl_last_error.restype = C.c_char_p
         L.cmbl_info.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(C.c_char_p),
                                 C.POINTER(C.c_char_p)]
+        L.cmbl_theory_len.argtypes = [vp]
         L.cmbl_derived_info.argtypes = [vp, C.POINTER(i), C.POINTER(C.c_char_p)]
         L.cmbl_derived_batch.argtypes = [vp, i, vp, ll, vp, ll, vp]
         L.cmbl_workspace_size.argtypes = [vp, i]
         L.cmbl_workspace_size.restype = sz
         L.cmbl_loglike_batch.argtypes = [vp, i, vp, ll, ll, vp, ll, vp, vp, vp]
+        L.cmbl_loglike_batch_sparse.argtypes = [vp, i, vp, ll, ll, vp, ll, vp, vp, vp, vp]
         L.cmbl_loglike_batch_host.argtypes = [vp, i, vp, ll, ll, vp, ll, vp]
         L.cmbl_clik_compute_batch.argtypes = [vp, i, vp, vp, ll, vp, vp, vp]
         L.cmbl_clik_workspace_size.argtypes = [vp, i]
@@ -135,6 +137,7 @@ def lib():
         L.cmbt_derived_count.argtypes = [vp]
         L.cmbt_derived_eval.argtypes = [vp, i, vp, ll, i, vp, ll, vp, vp]
         L.cmbs_set_theory_calculator.argtypes = [vp, vp]
+        L.cmbs_set_like_calculator.argtypes = [vp, i, vp]
         L.cmbg_create.argtypes = [vp, C.POINTER(CmbgConfig), C.POINTER(vp), C.c_char_p, sz]
         L.cmbg_destroy.argtypes = [vp]
         L.cmbg_last_error.argtypes = [vp]

@@ -101,6 +101,7 @@ int cmbl_open(const char *tag, const char *dataset_path, const char *override_in
         // tag -> likelihood class as CMBLikelihood_Add (source/CMB.f90:80-97)
         if (t == "PLIK_LITE") h->like = cmamd::make_plik_lite(ini);
         else if (t == "SPTPOL_TEEE" || t == "SPTPOL_BB") h->like = cmamd::make_sptpol(ini, t);   // CMB.f90:86-91
+        else if (t == "JLA") h->like = cmamd::make_jla(ini);   // JLALikelihood_Add (supernovae_JLA.f90:221-262)
         else if (t == "WMAP")   // CMB.f90:75-84: needs the external WMAP likelihood library
             cmamd::fail(CMBL_ERR_UNSUPPORTED, "cmbl_open: dataset tag '%s' not supported", tag);
         else h->like = cmamd::make_cmblikes(ini, t);      // TCMBLikes, TBK_planck (BKPLANCK), TSmica_planck (SMICA)
@@ -125,6 +126,8 @@ int cmbl_info(const cmbl_t *h, int *n_nuis, int *cl_lmax, int *speed, const char
     if (nuisance_names) *nuisance_names = L.nuisance_names.c_str();
     return CMBL_OK;
 }
+
+int cmbl_theory_len(const cmbl_t *h) { return h && h->like ? h->like->theory_len : 0; }
 
 int cmbl_derived_info(const cmbl_t *h, int *n_derived, const char **derived_names) {
     if (!h || !h->like) return CMBL_ERR_ARG;
@@ -152,7 +155,23 @@ int cmbl_loglike_batch(cmbl_t *h, int W, const double *dl, long long ld_field, l
         h->like->loglike_batch(W, dl, ld_field, ld_walker, nuis, ld_nuis, out, workspace, (hipStream_t)stream);
     });
 }
-
+int cmbl_loglike_batch_sparse(cmbl_t *h, int W, const double *dl, long long ld_field, long long ld_walker,
+                              const double *nuis, long long ld_nuis, double *out, void *workspace, void *stream,
+                              const int *wcount) {
+    if (!h || !h->like) return CMBL_ERR_ARG;
+    return guarded(&h->like->last_error, [&] {
+        if (W < 0 || (W > 0 && (!dl || !out || !wcount)))
+            cmamd::fail(CMBL_ERR_ARG, "cmbl_loglike_batch_sparse: bad arguments");
+        if (!h->like->sparse_capable())
+            cmamd::fail(CMBL_ERR_UNSUPPORTED, "%s: no sparse evaluation", h->like->name.c_str());
+        if (!workspace) {
+            h->like->own_ws.grow(h->like->workspace_size(W));
+            workspace = h->like->own_ws.p;
+        }
+        h->like->loglike_batch_sparse(W, dl, ld_field, ld_walker, nuis, ld_nuis, out, workspace, (hipStream_t)stream,
+                                      wcount);
+    });
+}
 
 int cmbl_loglike_batch_host(cmbl_t *h, int W, const double *dl, long long ld_field, long long ld_walker,
                             const double *nuis, long long ld_nuis, double *out) {
@@ -453,6 +472,11 @@ int cmbs_add_derived_likelihood(cmbs_t *s, cmbg_t *g) {
 int cmbs_set_theory_calculator(cmbs_t *s, cmbt_t *calc) {
     if (!s) return CMBL_ERR_ARG;
     return guarded(&s->last_error, [&] { cmamd::sampler_set_theory_calculator(s, calc); });
+}
+
+int cmbs_set_like_calculator(cmbs_t *s, int like_index, cmbt_t *calc) {
+    if (!s) return CMBL_ERR_ARG;
+    return guarded(&s->last_error, [&] { cmamd::sampler_set_like_calculator(s, like_index, calc); });
 }
 
 int cmbs_collector_enable(cmbs_t *s, int sample_capacity) {

@@ -279,6 +279,9 @@ struct Like {
     }
     int speed = -1;
     int cl_lmax[16] = {0};
+    // A likelihood that reads no C_l (JLA's distance moduli): the doubles of
+    // one walker's theory, all in field 0; 0 for the CMB likelihoods
+    int theory_len = 0;
     std::string last_error;
     virtual size_t workspace_size(int W) const = 0;
     virtual void loglike_batch(int W, const double *dl, long long ld_field, long long ld_walker,
@@ -366,9 +369,11 @@ struct Like {
 
 // Doubles of one walker's theory the likelihood reads: fields in
 // cmbl_loglike_batch order (TT, TE, EE, TB, EB, BB, PT, PE, PB, PP), each
-// l = 0..cl_lmax of its pair; the last used field ends at its lmax.
+// l = 0..cl_lmax of its pair; the last used field ends at its lmax.  A
+// likelihood with a theory_len reads that many doubles of field 0.
 inline long long theory_extent(const Like &L, long long ld_field) {
     static const int fi[10] = {1, 2, 2, 3, 3, 3, 4, 4, 4, 4}, fj[10] = {1, 1, 2, 1, 2, 3, 1, 2, 3, 4};
+    if (L.theory_len) return L.theory_len;
     long long ext = 0;
     for (int f = 0; f < 10; f++) {
         const int lm = L.cl_lmax[(fi[f] - 1) * 4 + (fj[f] - 1)];
@@ -380,6 +385,7 @@ inline long long theory_extent(const Like &L, long long ld_field) {
 std::unique_ptr<Like> make_plik_lite(const Ini &ini);
 std::unique_ptr<Like> make_cmblikes(const Ini &ini, const std::string &tag);
 std::unique_ptr<Like> make_sptpol(const Ini &ini, const std::string &tag);   // SPTPOL_TEEE / SPTPOL_BB
+std::unique_ptr<Like> make_jla(const Ini &ini);                             // jla.hip
 
 }  // namespace cmamd
 

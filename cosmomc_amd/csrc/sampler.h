@@ -221,6 +221,11 @@ struct cmbs {
     // walkers whose trial lies outside its box
     cmbt *calc = nullptr;
     cmamd::DevBuf calc_fail;
+    // per-likelihood calculators (cmbs_set_like_calculator; not owned): the one
+    // that fills that likelihood's trial-theory buffer instead of calc, and the
+    // flags of one such launch on their way into calc_fail
+    cmbt *like_calc[cmamd::MAXLIKE] = {};
+    cmamd::DevBuf calc_fail2;
     // the sampler swapped accepted trial theories into the walkers' theory rows
     // (cmbs_step_theory / cmbs_step_drag); after a resume those rows must be
     // recomputed at the restored points (cmbs_refresh_theory) before stepping
@@ -308,6 +313,7 @@ void sampler_step_drag(cmbs *s, int n_steps, double dragging_steps, cmbs_theory_
 void sampler_step_theory(cmbs *s, int n_steps, cmbs_theory_fn fn, void *user, hipStream_t stream);
 void sampler_refresh_theory(cmbs *s, cmbs_theory_fn fn, void *user, hipStream_t stream);
 void sampler_set_theory_calculator(cmbs *s, cmbt *calc);
+void sampler_set_like_calculator(cmbs *s, int like_index, cmbt *calc);
 void sampler_add_derived_likelihood(cmbs *s, cmbg *g);
 void sampler_collector_enable(cmbs *s, int samp_capacity);
 void sampler_collector_add(cmbs *s, const int *steps, int nsteps, int min_update, int check_burn, hipStream_t st);

@@ -15,6 +15,13 @@ void sampler_set_theory_calculator(cmbs *s, cmbt *calc) {
     if (calc && !s->calc_fail.p) s->calc_fail.alloc((size_t)s->dc.ld * 4);
 }
 
+void sampler_set_like_calculator(cmbs *s, int like_index, cmbt *calc) {
+    if (like_index < 0 || like_index >= (int)s->likes.size()) fail(CMBL_ERR_ARG, "no likelihood %d", like_index);
+    s->like_calc[like_index] = calc;
+    if (calc && !s->calc_fail.p) s->calc_fail.alloc((size_t)s->dc.ld * 4);
+    if (calc && !s->calc_fail2.p) s->calc_fail2.alloc((size_t)s->dc.ld * 4);
+}
+
 // The slow entries write through two kinds of view: the trial theories, which
 // the calculator fills, and the walkers' theory rows, which take the accepted
 // and the refreshed theories
@@ -40,20 +47,52 @@ static bool same_theory_swap(const cmbs *s, size_t i) {
     return false;
 }
 
+// The calculator that fills likelihood i's trial-theory buffer: the override of
+// the first likelihood reading that buffer which has one
+// (cmbs_set_like_calculator), else the sampler's
+static cmbt *trial_calculator(const cmbs *s, size_t i) {
+    for (size_t j = 0; j < s->likes.size(); j++)
+        if (s->like_calc[j] && s->end_theory[j] == s->end_theory[i]) return s->like_calc[j];
+    return s->calc;
+}
+static bool any_like_calculator(const cmbs *s) {
+    for (size_t j = 0; j < s->likes.size(); j++)
+        if (s->like_calc[j]) return true;
+    return false;
+}
+
+// flag[w] |= more[w]: a walker fails when any of its calculators flags it
+__global__ void calc_fail_or(int *__restrict__ flag, const int *__restrict__ more, int W)
+{
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w < W && more[w] != 0) flag[w] = 1;
+}
+
 // The theory source: the trial theories at parameter rows Prows [np][ld], from
 // the theory function or, without one, from the calculator (one launch per
 // distinct buffer).  True when the calculator made them: calc_fail then flags
-// the walkers outside its box (apply_calc_fail after the likelihoods).
+// the walkers outside its box (apply_calc_fail after the likelihoods).  With
+// per-likelihood calculators each launch overwrites its own flags, so every
+// launch after the first writes calc_fail2, which is ORed into calc_fail.
 static bool fill_trial_theory(cmbs *s, cmbs_theory_fn fn, void *user, const double *Prows, hipStream_t stream) {
     if (fn) {
         if (fn(user, s->W, Prows, (long long)s->dc.ld, stream) != 0) fail(CMBL_ERR_ARG, "theory function failed");
         return false;
     }
+    const bool several = any_like_calculator(s);
+    bool first = true;
     for (size_t i = 0; i < s->likes.size(); i++) {
         const TheoryView &e = s->end_theory[i];
         if (trial_theory_seen(s, i)) continue;
-        theorycalc_eval(s->calc, s->W, Prows, (long long)s->dc.ld, s->np, writable(e), e.ld_field, e.ld_walker,
-                        s->calc_fail.as<int>(), stream);
+        int *flags = (several && !first) ? s->calc_fail2.as<int>() : s->calc_fail.as<int>();
+        theorycalc_eval(several ? trial_calculator(s, i) : s->calc, s->W, Prows, (long long)s->dc.ld, s->np,
+                        writable(e), e.ld_field, e.ld_walker, flags, stream);
+        if (several && !first) {
+            hipLaunchKernelGGL(calc_fail_or, dim3((s->W + 255) / 256), dim3(256), 0, stream, s->calc_fail.as<int>(),
+                               (const int *)flags, s->W);
+            HIP_CHECK(hipGetLastError());
+        }
+        first = false;
     }
     return true;
 }
@@ -87,7 +126,10 @@ static void check_slow_entry(const cmbs *s, const char *entry, cmbs_theory_fn fn
         if (s->likes[i].th.ld_walker == 0)
             fail(CMBL_ERR_ARG, "%s: likelihood %zu needs per-walker theory rows (ld_walker > 0)", entry, i);
     }
-    if (!fn && !s->calc) fail(CMBL_ERR_ARG, "%s needs a theory function or a theory calculator", entry);
+    if (!fn)
+        for (size_t i = 0; i < std::max<size_t>(s->likes.size(), 1); i++)
+            if (!(i < s->likes.size() ? trial_calculator(s, i) : s->calc))
+                fail(CMBL_ERR_ARG, "%s needs a theory function or a theory calculator", entry);
     check_derived_calc(s, entry);
 }
 

@@ -119,6 +119,18 @@ class NativeCMBLikelihood(DataLikelihood):
         N.check(rc, self._h)
         return out
 
+    def loglike_batch_sparse(self, dl, nuis, out, count, workspace=None):
+        """loglike_batch over the W slots of which only [0, count[0]) are live
+        (cmbl_loglike_batch_sparse; count a cuda int32 tensor): out of the
+        other slots is left as it is."""
+        ws = workspace.data_ptr() if workspace is not None else None
+        nptr, nld = (nuis.data_ptr(), nuis.stride(0)) if nuis.numel() > 0 else (None, 0)
+        rc = N.lib().cmbl_loglike_batch_sparse(self._h, dl.shape[0], dl.data_ptr(), dl.stride(1), dl.stride(0), nptr,
+                                               nld, out.data_ptr(), ws, N.current_stream_ptr(dl.device),
+                                               count.data_ptr())
+        N.check(rc, self._h)
+        return out
+
     def derived_batch(self, nuis, out=None):
         """derivedParameters(Theory, DataParams) for every walker
         (cmbl_derived_batch; GeneralTypes.f90:504-512, SMICA CMBlikes.f90:1324-1337):

@@ -151,6 +151,17 @@ class BatchedMCMC:
         self._calc = calc                            # not owned by the library: keep it alive
         self._check(N.lib().cmbs_set_theory_calculator(self._h, None if calc is None else calc.handle))
 
+    def set_like_calculator(self, like_index: int, calc):
+        """A calculator of its own for likelihood ``like_index``'s trial-theory
+        buffer (cmbs_set_like_calculator), e.g. JLA's distance moduli beside a
+        D_l buffer; the calculator of set_theory_calculator still serves the
+        rest and the derived likelihoods.  A trial outside any calculator's
+        box is rejected.  None removes the override."""
+        self._like_calcs = getattr(self, "_like_calcs", {})
+        self._like_calcs[like_index] = calc          # not owned by the library: keep it alive
+        self._check(N.lib().cmbs_set_like_calculator(self._h, int(like_index),
+                                                     None if calc is None else calc.handle))
+
     def _theory_cb(self, theory_fn):
         import torch
         if theory_fn is None:

@@ -67,7 +67,12 @@ typedef struct cmbl cmbl_t;
  * CMB_SPTpol_BB_2019.f90; sptpol_blind_r is CMBL_ERR_UNSUPPORTED), "SMICA"
  * CMBlikes with the SMICA TT foreground, nuisance_params and
  * calibration_paramname (TSmica_planck, CMBlikes.f90:1262-1339; binned HL or
- * gaussian), "WMAP" CMBL_ERR_UNSUPPORTED (external library), any other tag a CMBlikes
+ * gaussian), "JLA" the JLA supernova likelihood (supernovae_JLA.f90; a
+ * jla.dataset with the 16-column light-curve file and any of the six
+ * covariance components, file names as written or relative to the dataset;
+ * nuisance parameters alpha_JLA beta_JLA; JLA_marginalize = T and absdist_file
+ * are CMBL_ERR_UNSUPPORTED, a matrix of the wrong size or a set number outside
+ * 0..9 CMBL_ERR_FORMAT), "WMAP" CMBL_ERR_UNSUPPORTED (external library), any other tag a CMBlikes
  * dataset (CMBlikes.f90; like_approx HL or gaussian, binned, or exact,
  * unbinned: ExactChiSq CMBlikes.f90:967-979, up to 4 maps).
  * override_ini: "key = value" lines applied over the dataset file, as
@@ -83,6 +88,14 @@ const char *cmbl_last_error(const cmbl_t *h);
  * .paramnames (pointer owned by the handle). */
 int  cmbl_info(const cmbl_t *h, int *n_nuis, int *cl_lmax, int *speed,
                const char **name, const char **nuisance_names);
+
+/* Theory of a likelihood that reads no C_l: the doubles of one walker's theory
+ * row, all in field 0 (dl[w * ld_walker + i], i = 0 .. len-1; ld_field unused).
+ * JLA: its nsn distance moduli 5 log10((1+zhel_i)(1+zcmb_i) D_A(zcmb_i) / Mpc)
+ * (supernovae_JLA.f90:1195-1199), its cl_lmax all zero.  0 for the CMB
+ * likelihoods.  A calculator serves such a row with n_fields = 1, fields = {0},
+ * lmax = len - 1. */
+int  cmbl_theory_len(const cmbl_t *h);
 
 /* Derived parameters a likelihood outputs per sample (the '*' names of its
  * nuisance .paramnames): their count and space-separated names (pointer owned
@@ -113,12 +126,25 @@ int  cmbl_loglike_batch(cmbl_t *h, int W,
                         const double *nuis, long long ld_nuis,
                         double *out, void *workspace, void *stream);
 
+/* The same launch over W walker slots of which only [0, *wcount) are live
+ * (wcount a device int, read by the kernels): the sampler's per-likelihood
+ * change mask evaluates a likelihood this way on the compacted walkers whose
+ * parameters moved.  out of a slot at or beyond *wcount is not written.  A live
+ * slot's result has the bits cmbl_loglike_batch gives the same inputs.
+ * CMBL_ERR_UNSUPPORTED for a likelihood without the sparse form (exact
+ * CMBlikes, SPTpol). */
+int  cmbl_loglike_batch_sparse(cmbl_t *h, int W,
+                               const double *dl, long long ld_field, long long ld_walker,
+                               const double *nuis, long long ld_nuis,
+                               double *out, void *workspace, void *stream, const int *wcount);
+
 /* Same with HOST arrays: stages through pinned host memory and device buffers
  * the handle keeps between calls (no allocation per call once sized), runs on
  * the handle's own stream and synchronises.  For hosts that keep C_l in CPU
  * memory, e.g. the reference's LogLike called per evaluation with W = 1
  * (INTEGRATION.md).  Reads only the theory the likelihood uses: fields up to
- * the last with cl_lmax > 0, each to its lmax.  One host call at a time per
+ * the last with cl_lmax > 0, each to its lmax (cmbl_theory_len doubles of
+ * field 0 for a likelihood that has one).  One host call at a time per
  * handle (serialised internally). */
 int  cmbl_loglike_batch_host(cmbl_t *h, int W,
                              const double *dl, long long ld_field, long long ld_walker,
@@ -368,6 +394,16 @@ int  cmbt_derived_eval(cmbt_t *t, int M, const double *P, long long ld, int num_
  * sampler's use of it, and it is not part of the cmbs_save_state image (a
  * resumed run sets it again). */
 int  cmbs_set_theory_calculator(cmbs_t *s, cmbt_t *calc);
+/* A calculator of its own for likelihood like_index's trial-theory buffer
+ * (e.g. JLA's distance moduli beside a D_l buffer): it fills that buffer in
+ * place of the sampler's calculator, which still serves every other buffer and
+ * the derived likelihoods.  A walker fails -- logZero in every term row -- when
+ * any of the calculators flags it.  Likelihoods that share one trial buffer
+ * share its calculator (the first override among them).  cmbs_refresh_theory
+ * and the failure rule are as above; with no override set every launch is as
+ * without this call.  NULL removes the override.  Not owned, and not part of
+ * the cmbs_save_state image. */
+int  cmbs_set_like_calculator(cmbs_t *s, int like_index, cmbt_t *calc);
 
 /* ------------------------------------------------------------------ */
 /* Gaussian likelihood on calculator-derived quantities: the reference's
