@@ -43,6 +43,141 @@ def test_indefinite_case_is_logzero_exactly(goldens):
     assert sn.jla_loglike_host(g.dataset, g.ab[2, 0], g.ab[2, 1], g.mu[2]) == 1e30
 
 
+def _longdouble(D, ab, mu):
+    r = [jf.jla_loglike_longdouble(D, a, b, m) for (a, b), m in zip(ab, mu)]
+    return np.array([v for v, _ in r]), np.array([p for _, p in r])
+
+
+def _host(D, ab, mu):
+    return np.array([sn.jla_loglike_host(D, a, b, m) for (a, b), m in zip(ab, mu)])
+
+
+@pytest.mark.parametrize("name", jf.NAMES)
+def test_longdouble_restatement_matches_reference(goldens, name):
+    """The long-double restatement (the reference of test_gpu_jla_edges.py)
+    against the compiled reference and against the float64 restatement: 1e-13,
+    LOGZERO exactly where ref.txt has it.  ref.txt itself is a float64 result."""
+    g = goldens[name]
+    D = sn.JLADataset(g.dataset)
+    ld, bad = _longdouble(D, g.ab, g.mu)
+    host = _host(D, g.ab, g.mu)
+    zero = g.ref == jf.LOGZERO
+    assert np.array_equal(ld == jf.LOGZERO, zero) and np.array_equal(bad >= 0, zero)
+    assert np.array_equal(host == jf.LOGZERO, zero)
+    print(name, jf.rel_distance(g.ref[~zero], ld[~zero]), jf.rel_distance(host[~zero], ld[~zero]))
+    assert jf.rel_distance(g.ref[~zero], ld[~zero]) < 1e-13
+    assert jf.rel_distance(host[~zero], ld[~zero]) < 1e-13
+
+
+def test_longdouble_first_bad_pivot_of_golden(goldens):
+    """syn5_indef: one block column, so any row of it may be the first to fail; the pivot before it is positive."""
+    g = goldens["syn5_indef"]
+    v, p = jf.jla_loglike_longdouble(sn.JLADataset(g.dataset), g.ab[2, 0], g.ab[2, 1], g.mu[2])
+    assert v == jf.LOGZERO and 0 <= p < 5
+    assert jf.jla_loglike_longdouble(sn.JLADataset(g.dataset), np.nan, 0.0, g.mu[0]) == (jf.LOGZERO, 0)
+
+
+def test_write_dataset_round_trip(tmp_path):
+    """write_dataset on what make_synthetic wrote gives the same dataset, and places single entries as given."""
+    ds, mu, ab = jf.make_synthetic(str(tmp_path / "a"), 7, ("mag", "stretch_colour"), True, 77)
+    names, rows = jf.read_lc(str(tmp_path / "a"))
+    mats = {k: jf.read_matrix(str(tmp_path / "a" / (k + ".dat"))) for k in ("mag", "stretch_colour")}
+    ds2 = jf.write_dataset(str(tmp_path / "b"), names, rows, mats, True)
+    for f in ("lc.txt", "jla.dataset", "mag.dat", "stretch_colour.dat"):
+        assert open(tmp_path / "a" / f).read() == open(tmp_path / "b" / f).read(), f
+    mats["mag"][5, 2] += 1.0                    # strict lower triangle: not read
+    mats["mag"][2, 5] -= 0.25
+    D = sn.JLADataset(jf.write_dataset(str(tmp_path / "c"), names, rows, mats, True))
+    E = sn.JLADataset(ds2)
+    assert D.comp["mag"][5, 2] == D.comp["mag"][2, 5] == E.comp["mag"][2, 5] - 0.25
+    assert (D.comp["mag"] != E.comp["mag"]).sum() == 2
+
+
+# ---- input conditions of the datasets of test_gpu_jla_edges.py: a generator that drifts fails here
+
+@pytest.mark.parametrize("nsn,p", jf.PIVOT)
+def test_edge_pivot_inputs(nsn, p):
+    """V(0.2, 1) fails first at pivot p exactly, the two other cases are positive definite."""
+    e = jf.edge("pivot_%d_%d" % (nsn, p))
+    assert e.D.nsn == nsn and sorted(e.D.comp) == ["mag", "stretch"] and e.D.twoscriptmfit
+    assert list(e.bad) == [p, -1, -1]
+    assert list(e.ref == jf.LOGZERO) == [True, False, False]
+    host = _host(e.D, e.ab, e.mu)
+    assert host[0] == jf.LOGZERO and jf.rel_distance(host[1:], e.ref[1:]) < 1e-13
+    # the pivots before p do not depend on S[p, p]: without it the case is positive definite
+    S = e.D.comp["stretch"]
+    assert S[p, p] == -jf.PIVOT_S and np.count_nonzero(S) == 1
+    assert np.linalg.eigvalsh(jf.jla_V(e.D, *e.ab[0]) - e.ab[0, 0] ** 2 * S).min() > 0
+
+
+@pytest.mark.parametrize("name", [n for n in jf.EDGE_NAMES if n.split("_")[0] in ("slabs", "subset", "diag300")])
+def test_edge_finite_inputs(name):
+    """No case is LOGZERO in the long-double reference, and the float64 restatement sits at 1e-13 of it."""
+    e = jf.edge(name)
+    kind, _, arg = name.partition("_")
+    if kind == "slabs":
+        assert e.D.nsn == int(arg.split("_")[0]) and sorted(e.D.comp) == sorted(jf.COMPONENTS)
+        assert e.D.twoscriptmfit == bool(int(arg.split("_")[1]))
+        T = (e.D.nsn + 15) // 16
+        assert ((T + 3) // 4 > 4) == (e.D.nsn == 257)         # slabs of block column 0: a second lap at 257 only
+    elif kind == "subset":
+        assert e.D.nsn == 33 and sorted(e.D.comp) == sorted(jf.SUBSETS[arg]) and e.D.twoscriptmfit
+    else:
+        assert e.D.nsn == 300 and e.D.diag_errors and e.D.twoscriptmfit == bool(int(arg))
+    assert len(e.ref) == 3 and np.all(e.bad == -1)
+    assert np.all(np.isfinite(e.ref.astype(np.float64))) and np.all(e.ref < 1e4)
+    d = jf.rel_distance(_host(e.D, e.ab, e.mu), e.ref)
+    print(name, [float(x) for x in e.ref], d)
+    assert d < 1e-13
+
+
+def test_edge_subsets_share_the_zero_case():
+    """alpha = beta = 0 leaves only mag of V's components: the datasets without it agree there exactly."""
+    assert list(jf.edge("subset_mag").ab[1]) == [0.0, 0.0]
+    ref = [jf.edge("subset_" + k).ref[1] for k in jf.SUBSETS if k != "mag"]
+    assert len(ref) == 6 and all(r == ref[0] for r in ref) and ref[0] != jf.edge("subset_mag").ref[1]
+
+
+def test_edge_illcond_inputs():
+    e = jf.edge("illcond")
+    assert e.D.nsn == 230 and sorted(e.D.comp) == ["mag"] and not e.D.cov_ms.any()
+    cond = [np.linalg.cond(jf.jla_V(e.D, a, b)) for a, b in e.ab]
+    d = jf.rel_distance(_host(e.D, e.ab, e.mu), e.ref)
+    print(cond, [float(x) for x in e.ref], d)
+    assert min(cond) >= 1e6 and np.all(e.bad == -1)
+    assert d < 1e-11
+
+
+@pytest.fixture(scope="module")
+def upper(tmp_path_factory):
+    return jf.extract(tmp_path_factory.mktemp("jla_upper"), jf.GOLDEN_UPPER, jf.NAMES_UPPER)["syn21_upper"]
+
+
+def test_upper_triangle_is_the_one_read(upper):
+    """syn21_upper: matrix files whose strict lower triangles are noise, one of
+    them a number a line.  Both restatements (np.triu) match the compiled
+    reference; the same files read by their lower triangle do not."""
+    d = os.path.dirname(upper.dataset)
+    files = {k: jf.read_matrix(os.path.join(d, k + ".dat")) for k in ("mag", "stretch", "mag_colour")}
+    assert all(not np.allclose(m, m.T) for m in files.values())
+    assert len(open(os.path.join(d, "stretch.dat")).read().split("\n")) == 21 * 21 + 2
+    D = sn.JLADataset(upper.dataset)
+    assert D.nsn == 21 and sorted(D.comp) == ["mag", "mag_colour", "stretch"] and not D.twoscriptmfit
+    for k, m in files.items():
+        assert np.array_equal(D.comp[k], np.triu(m) + np.triu(m, 1).T)
+    assert np.all(upper.ref < 1e4)
+    host = _host(D, upper.ab, upper.mu)
+    ld, bad = _longdouble(D, upper.ab, upper.mu)
+    print(jf.rel_distance(upper.ref, ld), jf.rel_distance(host, ld))
+    np.testing.assert_allclose(host, upper.ref, rtol=1e-13, atol=0)
+    assert np.all(bad == -1) and jf.rel_distance(upper.ref, ld) < 1e-13
+    for k, m in files.items():
+        D.comp[k] = np.tril(m) + np.tril(m, -1).T
+    lower = _host(D, upper.ab, upper.mu)
+    print(lower)
+    assert np.all(np.abs(lower / upper.ref - 1) > 1e-6)
+
+
 def test_dataset_tables(goldens):
     D = sn.JLADataset(goldens["syn131"].dataset)
     assert D.nsn == 131 and D.twoscriptmfit and not D.diag_errors

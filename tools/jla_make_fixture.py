@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
-"""Inputs of the JLA goldens (tests/golden/jla/jla_fixture.tar.xz).
+"""Inputs of the JLA goldens (tests/golden/jla/jla_fixture.tar.xz, jla_upper.tar.xz).
 
   python tools/jla_make_fixture.py --lcparams <reference>/data/jla_lcparams.txt --out DIR
   (run tools/jla_ref_harness on every DIR/<name>, see its header)
   python tools/jla_make_fixture.py --pack DIR
+
+--archive upper does the same for the second archive (default: fixture); each
+archive is made and packed on its own, so one can be added without touching
+the other.
 
 Seeded (np.random.RandomState, whose stream is frozen) synthetic datasets: SN
 rows taken from the JLA light-curve file, component matrices cut from one
@@ -13,6 +17,13 @@ beta; pecz = 0.0005, intrinsicdisp = 0.1 and intrinsicdisp1 = 0.08 so those
 paths differ from their defaults.  syn5_indef instead has a mag_stretch matrix
 that makes V indefinite at (0.2, 2.5) only.  Every number is written to 9
 significant digits; the archive holds text data only.
+
+syn21_upper (jla_upper.tar.xz) tells the two triangles of a matrix file apart:
+the reference reads mat(j, 1:n) row by row and DPOTRF takes the upper triangle
+only (:329-331, 135), so the strict lower triangle of every matrix file is
+overwritten with seeded noise of the entries' own scale; a loader that read it
+would give another, usually still finite, answer.  Its stretch matrix is
+written one number a line, the reference's second layout (:335-342).
 """
 import argparse
 import io
@@ -29,6 +40,8 @@ DATASETS = [("syn37", 37, tuple(BLOCK), True, 3701),
             ("syn131", 131, ("mag", "stretch", "mag_colour"), True, 13101),
             ("syn37_diag", 37, (), True, 3702),
             ("syn5_indef", 5, ("mag", "mag_stretch"), False, 501)]
+UPPER = [("syn21_upper", 21, ("mag", "stretch", "mag_colour"), False, 2101)]
+ARCHIVES = {"fixture": ("jla_fixture.tar.xz", DATASETS), "upper": ("jla_upper.tar.xz", UPPER)}
 FILES = ["jla.dataset", "lc.txt", "cases.txt", "ref.txt"] + [k + ".dat" for k in BLOCK]
 
 
@@ -36,11 +49,11 @@ def g9(x):
     return "%.9g" % x
 
 
-def write_matrix(path, M):
+def write_matrix(path, M, flat=False):
     with open(path, "w") as f:
         f.write("%d\n" % len(M))
         for r in M:
-            f.write(" ".join(g9(x) for x in r) + "\n")
+            f.write(("\n" if flat else " ").join(g9(x) for x in r) + "\n")
 
 
 def diag_terms(d, a, b):
@@ -85,11 +98,15 @@ def make(name, n, comps, two, seed, src, out):
             c *= 1.05
         assert all(mineig(c, a, b) > 1e-3 for a, b in CASES if a != 0.2), c
         mats["mag_stretch"] = -c * B
+    if name == "syn21_upper":
+        for k in comps:
+            noise = np.std(mats[k]) * rng.standard_normal((n, n))
+            mats[k] = np.triu(mats[k]) + np.tril(noise, -1)
     with open(os.path.join(out, "jla.dataset"), "w") as f:
         f.write("name = JLA%s\ndata_file = lc.txt\npecz = 0.0005\nintrinsicdisp = 0.1\nintrinsicdisp1 = 0.08\n" % name)
         f.write("twoscriptmfit = %s\nscriptmcut = 10.0\n" % ("T" if two else "F"))
         for k in comps:
-            write_matrix(os.path.join(out, k + ".dat"), mats[k])
+            write_matrix(os.path.join(out, k + ".dat"), mats[k], flat=name == "syn21_upper" and k == "stretch")
             f.write("has_%s_covmat = T\n%s_covmat_file = %s.dat\n" % (k, k, k))
     zc = d[:, 0]
     mu0 = 5 * np.log10((1 + zc) * zc * (1 + 0.5 * zc) * 299792.458 / 70) + 25
@@ -101,12 +118,13 @@ def make(name, n, comps, two, seed, src, out):
             f.write(" ".join(g9(x) for x in mu) + "\n")
 
 
-def pack(root):
+def pack(root, archive="fixture"):
+    fname, datasets = ARCHIVES[archive]
     dst = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "jla")
     os.makedirs(dst, exist_ok=True)
     buf = io.BytesIO()
     with tarfile.open(fileobj=buf, mode="w:xz", preset=9) as tar:
-        for name, *_ in DATASETS:
+        for name, *_ in datasets:
             for fn in FILES:
                 p = os.path.join(root, name, fn)
                 if not os.path.exists(p):
@@ -117,9 +135,9 @@ def pack(root):
                 data = open(p, "rb").read()
                 ti.size, ti.mtime, ti.mode = len(data), 0, 0o644
                 tar.addfile(ti, io.BytesIO(data))
-    with open(os.path.join(dst, "jla_fixture.tar.xz"), "wb") as f:
+    with open(os.path.join(dst, fname), "wb") as f:
         f.write(buf.getvalue())
-    print("wrote", os.path.join(dst, "jla_fixture.tar.xz"), len(buf.getvalue()), "bytes")
+    print("wrote", os.path.join(dst, fname), len(buf.getvalue()), "bytes")
 
 
 def main():
@@ -127,11 +145,12 @@ def main():
     ap.add_argument("--lcparams")
     ap.add_argument("--out")
     ap.add_argument("--pack")
+    ap.add_argument("--archive", choices=sorted(ARCHIVES), default="fixture")
     a = ap.parse_args()
     if a.pack:
-        return pack(a.pack)
+        return pack(a.pack, a.archive)
     src = [l for l in open(a.lcparams) if not l.lstrip().startswith("#")]
-    for name, n, comps, two, seed in DATASETS:
+    for name, n, comps, two, seed in ARCHIVES[a.archive][1]:
         make(name, n, comps, two, seed, src, os.path.join(a.out, name))
         print("wrote", os.path.join(a.out, name))
 
