@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void sptpol_window_kernel(SPDev c, const doubl
             for (int s = 0; s < LPL; s++) dst[1 + s] = lb + s <= lcap ? Df[lb + s] : 0.0;
         }
         if (KIND == SP_TEEE) {
-            dst[0] = Df[lb - 1];
+            dst[0] = lb - 1 <= lcap ? Df[lb - 1] : 0.0;
             dst[LPL + 1] = lb + LPL <= lcap ? Df[lb + LPL] : 0.0;
         }
     };

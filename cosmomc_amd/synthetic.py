@@ -440,6 +440,187 @@ def make_sptpol_bb(seed: int = 2019) -> SptpolBBData:
 
 
 # ---------------------------------------------------------------------------
+# SPTpol window geometries.  make_sptpol_teee / make_sptpol_bb taper every window
+# to (almost) nothing at the ends of the l range, so a likelihood that misreads
+# the first or last multipoles, or the l-1 / l+1 halo of the TE/EE derivative,
+# still agrees with them.  The datasets below put full weight on those entries
+# and lay the windows out so that every branch of the work-item builder runs.
+# A bin is (first l, last l), or None for a window that is zero everywhere.
+
+def _split(lo: int, hi: int, n: int) -> list[tuple[int, int]]:
+    """n consecutive bins that cover lo..hi, as equal as integers allow."""
+    e = [lo + (i * (hi - lo + 1)) // n for i in range(n + 1)]
+    return [(e[i], e[i + 1] - 1) for i in range(n)]
+
+
+def _tophat_windows(lmin: int, lmax: int, bins: list, u: np.ndarray) -> np.ndarray:
+    """Dense window columns [lmax-lmin+1, len(bins)]: over each bin the weights
+    0.5 + u (u consumed in column order), normalised to unit sum, so the first
+    and last l of a bin weigh as much as any other and no two l weigh the same."""
+    out = np.zeros((lmax - lmin + 1, len(bins)))
+    at = 0
+    for b, e in enumerate(bins):
+        if e is None:
+            continue
+        n = e[1] - e[0] + 1
+        v = 0.5 + u[at:at + n]
+        at += n
+        out[e[0] - lmin:e[1] - lmin + 1, b] = v / v.sum()
+    return out
+
+
+def _geom_data(win: np.ndarray, base: np.ndarray, g: np.ndarray, frac: float) -> tuple[np.ndarray, np.ndarray]:
+    """Bandpowers of ``base`` [band][l of the windows] and their covariance.
+
+    The error of a bandpower whose window spans n l is frac * sqrt(20 / n) of it
+    (a wide bin is known better than a narrow one); one whose window is zero,
+    so that its model bandpower is 0, takes 1 % of the rms of ``base`` with an
+    error of 10 * frac of that.  Every bandpower is scattered by one such
+    error, and the covariance is _spd_cov's correlation scaled to the errors:
+    _spd_cov's common floor is left out, under which the small low-l EE and BB
+    bandpowers would not feel their windows' first l, nor a 2000-l bin a single one."""
+    nb = win.shape[1] // base.shape[0]
+    v = np.concatenate([win[:, k * nb:(k + 1) * nb].T @ b for k, b in enumerate(base)])
+    n = np.count_nonzero(win, axis=0)
+    v[n == 0] = 0.01 * np.sqrt(np.mean(base ** 2))
+    rel = np.where(n > 0, np.sqrt(20.0 / np.maximum(n, 1)), 10.0)
+    sc = np.abs(v) * rel
+    cov = sc[:, None] * _spd_cov(np.ones(v.size), g[v.size:], frac) * sc[None, :]
+    return v * (1.0 + frac * rel * g[:v.size]), cov
+
+
+# name -> (lmin, lmax, TE bins, EE bins)
+def sptpol_geom_teee_cases() -> dict:
+    zg = _split(20, 420, 33)
+    dj = [(21, 30)] + [None] * 14 + [(880, 900), (400, 401)]
+    cases = {
+        "lmin2": (2, 289, _split(2, 289, 3)),                   # halo at l = 1
+        "odd_lmin_17": (51, 370, _split(51, 370, 17)),          # first item from lmin - 1; column groups 16 + 1
+        "len256": (40, 295, _split(40, 295, 16)),               # union support of exactly 256 l
+        "len257": (40, 296, _split(40, 296, 16)),               # ... and of 257 l
+        "zero_group": (20, 420, [None] * 16 + zg[16:], zg),     # a TE column group without windows
+        "disjoint": (21, 900, dj),                              # wide union support, mostly zero weights
+        "nine_rows": (2, 2060, [(4, 2052)]),                    # 2049 l in one bin; 2 bandpowers in all
+        "all_zero": (30, 200, [None, None]),                    # no window at all
+    }
+    for lmin in (30, 31):                                       # one l at each end, every lmax mod 8
+        for lmax in range(193, 201):
+            cases[f"edge_sweep_{lmin}_{lmax}"] = (lmin, lmax, [(lmin, lmin), (lmax, lmax)])
+    return {k: (v[0], v[1], v[2], v[3] if len(v) > 3 else v[2]) for k, v in cases.items()}
+
+
+# name -> (lmin, lmax, bins of 150x150, 95x150, 95x95)
+def sptpol_geom_bb_cases() -> dict:
+    zb = [(30, 30)] + _split(31, 296, 5) + [(297, 297)]
+    return {
+        "bb_odd": (51, 370, [_split(51, 370, 7)] * 3),
+        "bb_17": (2, 289, [_split(2, 289, 17)] * 3),
+        "bb_zero_band": (30, 297, [zb, [None] * 7, zb]),        # single l at both ends; 95x150 has no windows
+    }
+
+
+def sptpol_geom_cases() -> dict:
+    """name -> tag of every geometry dataset."""
+    out = {k: "SPTPOL_TEEE" for k in sptpol_geom_teee_cases()}
+    out.update({k: "SPTPOL_BB" for k in sptpol_geom_bb_cases()})
+    return out
+
+
+def _geom_seed(name: str) -> int:
+    return 0x5E0 + 16 * list(sptpol_geom_cases()).index(name)
+
+
+def make_sptpol_geom(name: str):
+    """The geometry dataset ``name`` (SptpolTEEEData or SptpolBBData).  Every band
+    has its own window weights, also where the bands share their bin edges."""
+    seed = _geom_seed(name)
+    if name in sptpol_geom_teee_cases():
+        lmin, lmax, te, ee = sptpol_geom_teee_cases()[name]
+        nb, nl = len(te), lmax - lmin + 1
+        u = uniforms(seed, 2 * nl * nb)
+        win = np.hstack([_tophat_windows(lmin, lmax, te, u[:nl * nb]), _tophat_windows(lmin, lmax, ee, u[nl * nb:])])
+        base = base_theory(lmax + 1)[:, lmin:lmax + 1]
+        g = gaussians(seed + 1, 3 * nb + 4 * nb * nb + 4 * nb)
+        spec = np.zeros((3, nb))
+        v, cov = _geom_data(win, base[[FIELD_TE, FIELD_EE]], g, 0.03)
+        spec[:2] = v.reshape(2, nb)
+        spec[2] = (win[:, :nb].T @ base[FIELD_TT]) * (1.0 + 0.02 * g[2 * nb + 4 * nb * nb:3 * nb + 4 * nb * nb])
+        beam = 0.01 * g[3 * nb + 4 * nb * nb:].reshape(2, 2 * nb)
+        return SptpolTEEEData(lmin, lmax, win, spec, cov, beam)
+    lmin, lmax, bands = sptpol_geom_bb_cases()[name]
+    nb, nl = len(bands[0]), lmax - lmin + 1
+    u = uniforms(seed, 3 * nl * nb)
+    win = np.hstack([_tophat_windows(lmin, lmax, b, u[k * nl * nb:(k + 1) * nl * nb]) for k, b in enumerate(bands)])
+    base = base_theory(lmax + 1)[FIELD_BB, lmin:lmax + 1]
+    g = gaussians(seed + 1, 3 * nb + 9 * nb * nb + 21 * nb)
+    rt = make_sptpol_bb().r_template
+    # the foregrounds at the centre of sptpol_geom_nuisance (Poisson, galactic dust
+    # scaled from 150 GHz by about 1.08, 0.40, 0.15, tensors), kept below the lensing
+    # B modes so that the theory's first l still weighs in its bandpower.  The
+    # constant is left out: with it every walker's low-l model lies above the data
+    # by several errors, on one side, so none sits at the minimum of its chi^2,
+    # where -lnL would not feel a change of the theory to first order.
+    ell = np.arange(lmin, lmax + 1, dtype=np.float64)
+    dust = 1e-5 * ((ell + 1.0) / 81.0) * (80.0 / ell) ** 1.42
+    fg = [pois * ell * (ell + 1.0) / (3000.0 * 3001.0) + ds * dust + 0.001 * rt[lmin:lmax + 1]
+          for pois, ds in ((0.05, 1.08), (0.03, 0.40), (0.02, 0.15))]
+    v, cov = _geom_data(win, base[None, :] + np.array(fg), g, 0.08)
+    spec = v.reshape(3, nb)
+    beam = 0.005 * g[3 * nb + 9 * nb * nb:].reshape(7, 3 * nb)
+    edges = [e if e is not None else (lmin, lmax) for e in bands[0]]
+    return SptpolBBData(lmin, lmax, (152.3, 96.2), edges, win, spec, cov, beam, rt)
+
+
+def sptpol_geom_overrides(name: str, on: bool) -> dict:
+    """Dataset overrides of a geometry case.  ``on`` is correct_aberration for
+    TE/EE and sptpol_blind_abb for BB; the priors are always on (@DIR@ stands for
+    the dataset's directory)."""
+    if sptpol_geom_cases()[name] == "SPTPOL_TEEE":
+        return {"correct_aberration": "T" if on else "F", "sptpol_tcal_prior": "T", "sptpol_pcal_prior": "T",
+                "sptpol_kappa_prior": "T", "sptpol_meankappa": "0.02", "sptpol_sigmakappa": "0.004",
+                "sptpol_alphaEE_prior": "T", "sptpol_alphaTE_prior": "T"}
+    over = {"sptpol_cal_prior": "T", "sptpol_invCal_90x150": "0.0001", "sptpol_Add_prior": "T"}
+    if on:
+        over.update({"sptpol_blind_abb": "T", "sptpol_blind_abb_file": "@DIR@/sptpol_blind_abb.bin"})
+    return over
+
+
+def sptpol_geom_theory(name: str, W: int) -> np.ndarray:
+    """Rough per-walker D_l [W, 3 or 6, lmax + 2] for a geometry case:
+    walker_theory * (1 + 0.2 g) with g ~ N(0,1) per entry, so neighbouring l
+    differ by tens of per cent and the derivative and aberration terms of TE/EE
+    weigh in.  l = 1, which walker_theory leaves at 0, repeats l = 2."""
+    teee = sptpol_geom_cases()[name] == "SPTPOL_TEEE"
+    lmax = (sptpol_geom_teee_cases() if teee else sptpol_geom_bb_cases())[name][1]
+    nf = 3 if teee else 6
+    n = nf * (lmax + 2)
+    th = walker_theory(W, seed=_geom_seed(name) + 2, lmax=lmax + 1, n_fields=nf)
+    th[:, :, 1] = th[:, :, 2]
+    g = np.stack([gaussians(_geom_seed(name) + 3 + 1000 * (w + 1), n) for w in range(W)])
+    return th * (1.0 + 0.2 * g.reshape(W, nf, lmax + 2))
+
+
+def sptpol_geom_nuisance(name: str, W: int) -> np.ndarray:
+    """Per-walker DataParams [W, 11 or 16] for a geometry case: kappa near 0.02,
+    calibrations off 1, beam factors and dust amplitudes off 0.  BB walker 0 has
+    Abb == 1 and walker 1 has Abb == 0 exactly (the two special branches)."""
+    seed = _geom_seed(name) + 4
+    if sptpol_geom_cases()[name] == "SPTPOL_TEEE":
+        g = gaussians(seed, W * 11).reshape(W, 11)
+        c = np.array([0.02, 20.0, 0.05, 0.1, -2.42, 0.05, -2.42, 1.005, 1.005, 0.0, 0.0])
+        s = np.array([0.002, 0.2, 0.02, 0.02, 0.05, 0.01, 0.05, 0.002, 0.003, 1.0, 1.0])
+        return c[None, :] + g * s[None, :]
+    g = gaussians(seed, W * 16).reshape(W, 16)
+    c = np.array([1.0, 0.001, 3e-5, 1e-5, 0.05, 0.03, 0.02, 1.01, 0.98] + [0.0] * 7)
+    s = np.array([0.05, 0.0005, 3e-6, 3e-6, 0.01, 0.01, 0.01, 0.01, 0.01] + [1.0] * 7)
+    P = c[None, :] + g * s[None, :]
+    P[0, 0] = 1.0
+    if W > 1:
+        P[1, 0] = 0.0
+    return P
+
+
+# ---------------------------------------------------------------------------
 # BK15 (BASELINE configs[4]): the reference ships data/BK15 without its
 # bandpower covariance (BK15_dust.dataset: covmat_fiducial = BK15_covmat_dust.dat
 # is absent), so a synthetic SPD covariance of the file's shape is written next

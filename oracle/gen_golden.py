@@ -504,6 +504,37 @@ def gen_sptpol():
         json.dump(out, f, indent=1)
 
 
+# The SPTpol window geometries (cosmomc_amd.synthetic.make_sptpol_geom): every
+# case with its switch (correct_aberration for TE/EE, sptpol_blind_abb for BB)
+# off and on, the first SPTPOL_GEOM_WALKERS walkers of the seeded theory and
+# nuisances.  The fixture holds case names and results only; the inputs are
+# rebuilt from the case name.
+SPTPOL_GEOM_WALKERS = 3
+
+
+def gen_sptpol_geom():
+    W = SPTPOL_GEOM_WALKERS
+    out = {"generator": "cosmomc_amd.synthetic.make_sptpol_geom / sptpol_geom_theory / sptpol_geom_nuisance",
+           "switch": {"SPTPOL_TEEE": "correct_aberration", "SPTPOL_BB": "sptpol_blind_abb"},
+           "walkers": W, "cases": {}}
+    for name, tag in syn.sptpol_geom_cases().items():
+        with tempfile.TemporaryDirectory() as td:
+            path = syn.make_sptpol_geom(name).write(os.path.join(td, name))
+            th = syn.sptpol_geom_theory(name, W)
+            nu = syn.sptpol_geom_nuisance(name, W)
+            res = {"tag": tag}
+            for on in (False, True):
+                over = syn.sptpol_geom_overrides(name, on)
+                ini = f"cmb_dataset[{tag}] = {path}\n" + \
+                    "".join(f"cmb_dataset[{tag},{k}] = {v.replace('@DIR@', os.path.dirname(path))}\n"
+                            for k, v in over.items())
+                res["on" if on else "off"] = run_cmb_harness(ini, th, nu, td).tolist()
+            out["cases"][name] = res
+            print(f"{name:28s} -lnL = {res['on']}")
+    with open(os.path.join(GOLDEN, "sptpol_geom_ref.json"), "w") as f:
+        json.dump(out, f, indent=1)
+
+
 # TBaseParameters_SetFastSlowParams (BaseParameters.f90:302-433) through the
 # compiled reference (rng_harness "blocks"): (name, config dict); likes =
 # [(new_param_block_start, new_params, speed)] in the sorted list order
@@ -604,6 +635,7 @@ if __name__ == "__main__":
         gen_smica()
     if not only or "sptpol" in only:
         gen_sptpol()
+        gen_sptpol_geom()
     if not only or "exact" in only:
         gen_exact()
     if not only or "blocks" in only:

@@ -118,6 +118,7 @@ class SptpolTEEE:
                 cov[:nbin, :nbin] *= 1e24
             if self.TEonly:
                 cov[nbin:, nbin:] *= 1e24
+        self.cov = cov
         self.L = _chol(cov)
         wd = kv["sptpol_TEEE_window_dir"]
         self.windows = np.zeros((lmax - lmin + 1, nall))
@@ -253,6 +254,7 @@ class SptpolBB:
                     cov[t, :] = 0
                     cov[:, t] = 0
                     cov[t, t] = 1e12 * tmp
+        self.cov = cov
         self.L = _chol(cov)
         raw = np.fromfile(kv["sptpol_BB_window_file"], dtype="<u1")
         i0, i1 = np.frombuffer(raw[:8].tobytes(), dtype="<i4")
