@@ -112,7 +112,9 @@ __global__ __launch_bounds__(256) void cmbl_window_kernel(CLDev c, const double 
 #pragma unroll
         for (int u = 0; u < PER; u++) {
             const int r = rbase + 8 * u, w = w0 + r;
-            double v2[2] = {raw[u].x, raw[u].y};
+            // a 16-byte load at lq == it.l1 also brought l1 + 1 (behind lmax: the caller's row padding);
+            // its weight is 0, but 0 * NaN is NaN in the MFMA, so the slot holds 0
+            double v2[2] = {raw[u].x, lq + 1 <= it.l1 ? raw[u].y : 0.0};
             if (w < Wc && lq <= it.l1) {
                 const double *Df = dl + (long long)w * ld_walker + (long long)pr.field * ld_field;
 #pragma unroll
@@ -432,12 +434,15 @@ __global__ __launch_bounds__(256, 2) void cmbl_window_group(CLDev c, const GItem
                 dst[2][2 * s] = v2.x; dst[2][2 * s + 1] = v2.y;
                 dst[3][2 * s] = v3.x; dst[3][2 * s + 1] = v3.y;
             }
+            // an item of an odd first l starts at the even lmin - 1: zero weights and zero profiles
+            // there, but the theory entry is the caller's, and 0 * NaN is NaN in the MFMA
+            if (lb < c.lmin) dst[0][0] = 0.0;
         } else {
 #pragma unroll
             for (int s = 0; s < LPL; s++) {
                 const int l = lb + s;
                 const bool ok = l <= c.lmax;
-                dst[0][s] = ok ? Df[l] : 0.0;
+                dst[0][s] = ok && l >= c.lmin ? Df[l] : 0.0;
                 dst[1][s] = ok ? pw[l] : 0.0;
                 dst[2][s] = ok ? pw[LP + l] : 0.0;
                 dst[3][s] = ok ? pw[2 * LP + l] : 0.0;

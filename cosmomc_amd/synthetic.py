@@ -837,6 +837,203 @@ def make_smica(seed: int = 2015) -> SmicaData:
     return SmicaData(lmin, lmax, win, clhat, binned, noise, cov)
 
 
+# ---------------------------------------------------------------------------
+# CMBlikes window geometries.  The reference's own binned datasets and make_smica
+# fix lmin, lmax, the bin edges and the column counts at values nobody chose, and
+# make_smica's windows taper to nothing at both ends.  The datasets below are
+# small binned CMBLike2 datasets (the format of SmicaData.write, with one window
+# column per spectrum) whose windows put full weight on their first and last l and
+# are laid out so that every branch of the window work-item builder
+# (cmblikes.hip build_items) and of the three window kernels runs.  Segments are
+# the 256 l of a work item counted from cl_lmin.
+
+CMBL_GEOM_PAIRS = {"T": ("TT",), "T E": ("TT", "TE", "EE")}
+CMBL_GEOM_FIELD = {"TT": FIELD_TT, "TE": FIELD_TE, "EE": FIELD_EE}
+CMBL_GEOM_ABERRATION = 0.0012
+CMBL_GEOM_CAL_PRIOR = 0.0025
+
+
+def _rel(lmin: int, bins: list) -> list:
+    return [(lmin + a, lmin + b) for a, b in bins]
+
+
+# relative l (from lmin) of the seg_edges windows: ends at 255, 256, 257, 511, 512;
+# one window over all three segments; one l at lmin, at a segment's last and first l
+# (255, 256, 511, 512) and at lmax (558)
+_SEG_EDGES = [(0, 0), (1, 255), (100, 256), (200, 257), (255, 255), (256, 256), (258, 511), (300, 512), (0, 558),
+              (511, 511), (512, 512), (513, 557), (558, 558)]
+
+
+def cmbl_geom_geometries() -> dict:
+    """name -> (lmin, lmax, fields_use, bins of each spectrum TT[, TE, EE])."""
+    se = _rel(2, _SEG_EDGES)
+    return {
+        "full_even": (2, 600, "T", [_split(2, 600, 12)]),
+        "full_odd": (2, 601, "T", [_split(2, 601, 12)]),
+        "odd_lmin_17": (17, 400, "T", [_split(17, 400, 9)]),
+        "seg_edges": (2, 560, "T", [se]),
+        "seg_edges_te": (2, 560, "T E", [se, se, se]),
+        # 1, 16 and 17 columns in the three segments; 32 and 33 (one item of 32, one of 1) in two
+        # (the one window of the first segment is 40 l wide, so that the aberration rule at lmin weighs in it)
+        "cols_1_16_17": (2, 598, "T", [[(2, 41)] + _split(258, 513, 16) + _split(514, 598, 17)]),
+        "cols_32_33": (2, 513, "T", [_split(2, 257, 32) + _split(258, 513, 33)]),
+        # one bin per segment and spectrum; the nine items are 1, 4, 65 / 2, 31, 131 / 3, 222, 32 l long
+        "tails_mod4": (2, 644, "T E", [[(2, 2), (258, 261), (514, 578)], [(10, 11), (300, 330), (514, 644)],
+                                       [(20, 22), (260, 481), (514, 545)]]),
+        # TE and EE start on odd l inside the first segment (the item starts one l earlier, on a zero weight)
+        "three_pairs": (2, 300, "T E", [_split(2, 300, 6), _split(5, 290, 6), _split(3, 299, 6)]),
+    }
+
+
+def cmbl_geom_cases() -> dict:
+    """name -> (geometry, like_approx, aberration on, SMICA tag)."""
+    out = {k: (k, "gaussian", False, False) for k in ("full_even", "full_odd", "odd_lmin_17", "seg_edges",
+                                                      "cols_1_16_17", "cols_32_33", "tails_mod4", "three_pairs")}
+    out["hl_full_even"] = ("full_even", "HL", False, False)
+    out["hl_seg_edges_two_maps"] = ("seg_edges_te", "HL", False, False)
+    for k in ("full_even", "full_odd", "odd_lmin_17", "seg_edges"):
+        out["aber_" + k] = (k, "gaussian", True, False)
+    out["smica_even_top"] = ("full_even", "gaussian", False, True)
+    out["smica_even_top_aber"] = ("full_even", "gaussian", True, True)
+    # the staged kernel's second column block and chunk tails (aberration takes the direct kernel's cases there)
+    for k in ("cols_1_16_17", "cols_32_33", "tails_mod4"):
+        out["aber_" + k] = (k, "gaussian", True, False)
+    return out
+
+
+def cmbl_geom_tag(name: str) -> str:
+    return "SMICA" if cmbl_geom_cases()[name][3] else "GEOM"
+
+
+def _cmbl_geom_seed(name: str) -> int:
+    return 0xC6E0 + 16 * list(cmbl_geom_cases()).index(name)
+
+
+@dataclass
+class CmblGeomData:
+    lmin: int
+    lmax: int
+    fields: str             # fields_use: "T" or "T E"
+    bins: list              # per spectrum, per bin: (first l, last l)
+    windows: np.ndarray     # [lmax-lmin+1, nbin, nspec]
+    clhat: np.ndarray       # [nbin, nspec] binned signal
+    clfid: np.ndarray       # [nbin, nspec] fiducial (HL)
+    noise: np.ndarray       # [nbin, nspec] noise (HL)
+    cov: np.ndarray         # [nbin nspec, nbin nspec], index bin * nspec + spectrum
+    like_approx: str
+    aberration: float
+    smica: bool
+
+    @property
+    def pairs(self) -> tuple:
+        return CMBL_GEOM_PAIRS[self.fields]
+
+    @property
+    def nbin(self) -> int:
+        return self.clhat.shape[0]
+
+    def write(self, directory: str, extra: dict | None = None) -> str:
+        d = os.path.abspath(directory)
+        os.makedirs(os.path.join(d, "windows"), exist_ok=True)
+        nb, order = self.nbin, " ".join(self.pairs)
+        ell = np.arange(self.lmin, self.lmax + 1)
+        for b in range(nb):
+            np.savetxt(os.path.join(d, "windows", f"window{b + 1}.dat"),
+                       np.column_stack([ell, self.windows[:, b, :]]), fmt=["%d"] + ["%.17e"] * len(self.pairs))
+        for fn, v in (("clhat.dat", self.clhat), ("clfid.dat", self.clfid), ("noise.dat", self.noise)):
+            with open(os.path.join(d, fn), "w") as f:
+                f.write("#    L    " + "    ".join(self.pairs) + "\n")
+                for b in range(nb):
+                    f.write(f"{b + 1:6d} " + " ".join(f"{x:24.17e}" for x in v[b]) + "\n")
+        np.savetxt(os.path.join(d, "cov.dat"), self.cov, fmt="%.17e")
+        lines = ["dataset_format = CMBLike2", f"like_approx = {self.like_approx}", f"fields_use = {self.fields}",
+                 "binned = T", f"nbins = {nb}", f"cl_lmin = {self.lmin}", f"cl_lmax = {self.lmax}",
+                 "bin_window_files = windows/window%u.dat", f"bin_window_in_order = {order}",
+                 "cl_hat_file = clhat.dat", f"covmat_cl = {order}", "covmat_fiducial = cov.dat"]
+        if self.like_approx == "HL":
+            lines += ["cl_fiducial_file = clfid.dat", "cl_noise_file = noise.dat"]
+        if self.aberration != 0.0:
+            lines.append(f"aberration_coeff = {self.aberration!r}")
+        if self.smica:
+            with open(os.path.join(d, "smica.paramnames"), "w") as f:
+                for n, lab in SMICA_PARAMS:
+                    f.write(f"{n}    {lab}\n")
+                f.write("Dl2000_smica*    D_{2000}\n")
+            lines += ["nuisance_params = smica.paramnames", "calibration_paramname = cal_smica"]
+        else:
+            with open(os.path.join(d, "cal.paramnames"), "w") as f:
+                f.write("calPlanck    y_{\\rm cal}\n")
+            lines += ["calibration_param = cal.paramnames", f"log_calibration_prior = {CMBL_GEOM_CAL_PRIOR!r}"]
+        for k, v in (extra or {}).items():
+            lines.append(f"{k} = {v}")
+        path = os.path.join(d, "geom.dataset")
+        with open(path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+        return path
+
+
+def make_cmbl_geom(name: str) -> CmblGeomData:
+    """The window-geometry dataset ``name`` of cmbl_geom_cases().  Random positive
+    window weights (no two l of a window weigh the same, and every spectrum has
+    weights of its own), bandpowers of the best-fit theory (plus the fiducial
+    SMICA foreground for the SMICA tag) scattered by 0.7 of their 3 % errors, and
+    a correlated covariance of those errors.  HL: the unscattered bandpowers as
+    the fiducial, 2 % noise on TT and EE, and the observed spectra of a bin the
+    fiducial times one factor 1 + 0.02 g."""
+    gname, approx, aber, smica = cmbl_geom_cases()[name]
+    lmin, lmax, fields, bins = cmbl_geom_geometries()[gname]
+    pairs = CMBL_GEOM_PAIRS[fields]
+    seed = _cmbl_geom_seed(name)
+    nb, ns, nl = len(bins[0]), len(pairs), lmax - lmin + 1
+    assert all(len(b) == nb for b in bins)
+    u = uniforms(seed, ns * nl * nb)
+    win = np.stack([_tophat_windows(lmin, lmax, bins[k], u[k * nl * nb:(k + 1) * nl * nb]) for k in range(ns)], axis=2)
+    base = base_theory(lmax)[:, lmin:lmax + 1]
+    if smica:
+        base[FIELD_TT] = base[FIELD_TT] + smica_foreground(np.arange(lmin, lmax + 1, dtype=np.float64), SMICA_FG)
+    v = np.stack([win[:, :, k].T @ base[CMBL_GEOM_FIELD[p]] for k, p in enumerate(pairs)], axis=1)   # [nb, ns]
+    # 3 % errors, floored per spectrum at 0.3 % of its rms so that TE bins near a zero crossing keep a finite error
+    sig = 0.03 * np.sqrt(v ** 2 + 0.01 * np.mean(v ** 2, axis=0)[None, :])
+    n = nb * ns
+    g = gaussians(seed + 1, 2 * n + n * n)
+    M = np.eye(n) + 0.05 * (g[2 * n:].reshape(n, n) @ g[2 * n:].reshape(n, n).T) / n
+    cov = sig.ravel()[:, None] * M * sig.ravel()[None, :]
+    cov = 0.5 * (cov + cov.T)
+    clhat = v + 0.7 * sig * g[:n].reshape(nb, ns)
+    if approx == "HL":
+        # one factor per bin: the bin's matrix of observed spectra stays positive definite
+        # (independent scatter turns it indefinite where EE is tiny beside TE, at l = 2)
+        clhat = v * (1.0 + 0.02 * g[:n].reshape(nb, ns)[:, :1])
+    noise = 0.02 * np.abs(v) * (1.0 + 0.1 * np.abs(g[n:2 * n].reshape(nb, ns)))
+    for k, p in enumerate(pairs):
+        if p[0] != p[1]:
+            noise[:, k] = 0.0
+    return CmblGeomData(lmin, lmax, fields, bins, win, clhat, v, noise, cov, approx,
+                        CMBL_GEOM_ABERRATION if aber else 0.0, smica)
+
+
+def cmbl_geom_theory(name: str, W: int) -> np.ndarray:
+    """Per-walker D_l [W, 3, lmax + 1] (TT TE EE) for a geometry case:
+    walker_theory (walkers a per cent apart) times (1 + 0.03 g), g ~ N(0,1) per
+    entry, so that neighbouring l differ by a few per cent and the aberration
+    derivative weighs in at the ends of the range."""
+    lmax = cmbl_geom_geometries()[cmbl_geom_cases()[name][0]][1]
+    seed = _cmbl_geom_seed(name)
+    th = walker_theory(W, seed=seed + 2, lmax=lmax, n_fields=3)
+    g = np.stack([gaussians(seed + 3 + 1000 * (w + 1), 3 * (lmax + 1)) for w in range(W)])
+    return th * (1.0 + 0.03 * g.reshape(W, 3, lmax + 1))
+
+
+def cmbl_geom_nuisance(name: str, W: int) -> np.ndarray:
+    """Per-walker DataParams: the calibration, 1 + 0.0025 g ([W, 1]); for the SMICA
+    tag the five foreground parameters about SMICA_FG and the calibration ([W, 6])."""
+    seed = _cmbl_geom_seed(name) + 4
+    if not cmbl_geom_cases()[name][3]:
+        return 1.0 + 0.0025 * gaussians(seed, W).reshape(W, 1)
+    g = gaussians(seed, W * 6).reshape(W, 6)
+    return np.array(list(SMICA_FG) + [1.0])[None, :] + g * np.array([5.0, 0.1, 0.3, 3.0, 0.1, 0.0025])[None, :]
+
+
 def _py_gaussians(seed: int, n: int) -> list[float]:
     """gaussians() restated on Python floats and libm (math): the splitmix64
     uniforms are exact, and every later operation is one correctly ordered

@@ -535,6 +535,28 @@ def gen_sptpol_geom():
         json.dump(out, f, indent=1)
 
 
+# The CMBlikes window geometries (cosmomc_amd.synthetic.make_cmbl_geom): the first
+# CMBL_GEOM_WALKERS walkers of every case's seeded theory and nuisances.  The fixture
+# holds case names and results only; the inputs are rebuilt from the case name.
+CMBL_GEOM_WALKERS = 3
+
+
+def gen_cmbl_geom():
+    W = CMBL_GEOM_WALKERS
+    out = {"generator": "cosmomc_amd.synthetic.make_cmbl_geom / cmbl_geom_theory / cmbl_geom_nuisance",
+           "walkers": W, "cases": {}}
+    for name in syn.cmbl_geom_cases():
+        tag = syn.cmbl_geom_tag(name)
+        with tempfile.TemporaryDirectory() as td:
+            path = syn.make_cmbl_geom(name).write(os.path.join(td, name))
+            ref = run_cmb_harness(f"cmb_dataset[{tag}] = {path}\n", syn.cmbl_geom_theory(name, W),
+                                  syn.cmbl_geom_nuisance(name, W), td)
+            out["cases"][name] = {"tag": tag, "minus_lnL": ref.tolist()}
+            print(f"{name:28s} -lnL = {ref}")
+    with open(os.path.join(GOLDEN, "cmbl_geom_ref.json"), "w") as f:
+        json.dump(out, f, indent=1)
+
+
 # TBaseParameters_SetFastSlowParams (BaseParameters.f90:302-433) through the
 # compiled reference (rng_harness "blocks"): (name, config dict); likes =
 # [(new_param_block_start, new_params, speed)] in the sorted list order
@@ -636,6 +658,8 @@ if __name__ == "__main__":
     if not only or "sptpol" in only:
         gen_sptpol()
         gen_sptpol_geom()
+    if not only or "cmbl_geom" in only:
+        gen_cmbl_geom()
     if not only or "exact" in only:
         gen_exact()
     if not only or "blocks" in only:
