@@ -310,7 +310,7 @@ int cmbs_create(const cmbs_config_t *cfg, cmbs_t **out, char *errbuf, size_t err
     std::unique_ptr<cmbs> s(new cmbs);
     if (const char *e = std::getenv("CMAMD_PIPE")) {   // fast-step schedule for A/B runs (cmamd_debug_pipeline)
         const int m = std::atoi(e);
-        if (m == 0 || m == 3) s->pipe_mode = m;
+        if (m == 0 || m == 3) s->sched_mode = m;
         else   // modes 1, 2 and 4 were deleted in round 5: say so rather than run the default unannounced
             std::fprintf(stderr, "cosmomc_amd: CMAMD_PIPE=%s ignored (accepted: 0 unpipelined, 3 unified)\n", e);
     }
@@ -520,7 +520,7 @@ int cmbs_set_groups(cmbs_t *s, int n_groups) {
 
 int cmbs_set_binned_cache(cmbs_t *s, int on) {
     if (!s) return CMBL_ERR_ARG;
-    s->binned_cache = on != 0;
+    s->unified.binned_cache = on != 0;
     return CMBL_OK;
 }
 

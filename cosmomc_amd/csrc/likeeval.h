@@ -31,7 +31,7 @@ static EvalSet end_set(const cmbs *s) { return make_set(s, true, false); }
 static EvalSet start_set(const cmbs *s) { return make_set(s, false, true); }
 
 // a deferrable likelihood's evaluation for the accepting mh_kernel that follows:
-// the launches up to the quadratic form's partials, recorded in s->dc.def_*
+// the launches up to the quadratic form's partials, recorded in s->pending
 static bool is_deferred(const cmbs *s, size_t i) {
     for (int q : s->defer_likes)
         if (q == (int)i) return true;
@@ -39,11 +39,11 @@ static bool is_deferred(const cmbs *s, size_t i) {
 }
 
 static void record_deferred(cmbs *s, size_t i, const QFDeferred &d) {
-    const int p = s->pending_def++;
-    s->dc.def_like[p] = (int)i;
-    s->dc.def_items[p] = d.n_items;
-    s->dc.def_part[p] = d.partial;
-    s->dc.def_add[p] = d.addend;
+    const int p = s->pending.n++;
+    s->pending.like[p] = (int)i;
+    s->pending.items[p] = d.n_items;
+    s->pending.part[p] = d.partial;
+    s->pending.add[p] = d.addend;
 }
 
 // likelihood i is one of the fused window pass's pair
@@ -57,13 +57,16 @@ static bool fusable(const cmbs *s, const EvalSet &e) {
 }
 
 // the pass's two outputs on a set: each fused likelihood's window rows in the
-// set's workspace, calibrated by the set's DataParams
-static void fused_outs(const cmbs *s, const EvalSet &e, TPOut o[2]) {
+// set's workspace, calibrated by the set's DataParams.  With raw, the unified
+// launch's form: the sums into raw[k], the kind-1 stage bin-major
+// (steptail.h: its row stride is wpad(W))
+static void fused_outs(const cmbs *s, const EvalSet &e, TPOut o[2], const DevBuf *raw = nullptr) {
     for (int k = 0; k < 2; k++) {
         const int i = s->tp_like[k];
         const WinStage &st = s->tp_stage[k];
         Like &L = *s->likes[i].like->like;
-        o[k] = TPOut{st.kind, st.cal_index, st.ld, 0, L.window_out(e.ws[i], s->W), st.X, e.nuis[i],
+        o[k] = TPOut{st.kind, st.cal_index, raw && st.kind == 1 ? QuadForm::wpad(s->W) : st.ld, 0,
+                     raw ? raw[k].as<double>() : L.window_out(e.ws[i], s->W), st.X, e.nuis[i],
                      (long long)std::max(1, L.n_nuis)};
     }
 }
@@ -87,16 +90,20 @@ struct Corun {
     SmallGaussLaunch a{};
 };
 
+// likelihood i's whole after-window stage on a set as a small chi^2 that
+// another launch can carry (false: it is no such stage)
+static bool small_gauss_on(const cmbs *s, const EvalSet &e, int i, SmallGaussLaunch &g) {
+    Like &L = *s->likes[i].like->like;
+    return L.corun_small(g, s->W, e.nuis[i], L.n_nuis, e.terms[i], e.ws[i]);
+}
+
 static Corun plan_corun(cmbs *s, bool defer) {
     Corun c;
     if (!defer || !s->tpass || s->no_corun) return c;
     for (int k = 0; k < 2; k++) {
         const int h = s->tp_like[k], o = s->tp_like[1 - k];
-        Like &H = *s->likes[h].like->like;
-        Like &O = *s->likes[o].like->like;
-        if (!is_deferred(s, h) || !H.accepts_corun()) continue;
-        if (O.corun_small(c.a, s->W, s->dc.like_nuis[o], O.n_nuis, s->like_terms.as<double>() + o * (size_t)s->dc.ld,
-                          s->like_ws[o].p)) {
+        if (!is_deferred(s, h) || !s->likes[h].like->like->accepts_corun()) continue;
+        if (small_gauss_on(s, trial_set(s), o, c.a)) {
             c.carrier = h;
             c.carried = o;
             return c;
@@ -263,13 +270,10 @@ static bool eval_likes_drag_pair(cmbs *s, hipStream_t stream, bool both = true) 
         return false;
     const int W = s->W;
     Like &Q = *s->likes[qi].like->like;
-    Like &G = *s->likes[gi].like->like;
     QFSource qa, qb;
     if (!Q.qf_source(qa, W, a.ws[qi]) || !Q.qf_source(qb, W, b.ws[qi])) return false;
     SmallGaussLaunch ga{}, gb{};
-    if (!G.corun_small(ga, W, a.nuis[gi], G.n_nuis, a.terms[gi], a.ws[gi]) ||
-        !G.corun_small(gb, W, b.nuis[gi], G.n_nuis, b.terms[gi], b.ws[gi]))
-        return false;
+    if (!small_gauss_on(s, a, gi, ga) || !small_gauss_on(s, b, gi, gb)) return false;
     TPOut oa[2], ob[2];
     fused_outs(s, a, oa);
     fused_outs(s, b, ob);

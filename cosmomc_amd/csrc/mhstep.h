@@ -4,7 +4,7 @@
 // (included inside namespace cmamd)
 #pragma once
 
-// The unified step launch (pipe_mode 3): one launch per fast step.  Rows of
+// The unified step launch (sched_mode 3): one launch per fast step.  Rows of
 // workgroups (tail_rows) run step k's tails -- plik_lite's quadratic form from
 // raw sums and the lensing chi^2, which store write-through and arrive on
 // their walker tile's counter -- the window pass storing step k + 1's raw sums,

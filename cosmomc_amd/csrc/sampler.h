@@ -163,6 +163,68 @@ struct LikeSlot {
     TheoryView th;           // the walkers' theory
 };
 
+// Deferred combines the last evaluation left for the accepting launch that
+// follows (record_deferred; launch_cfg moves them into that launch's DevCfg)
+struct PendingDeferred {
+    int n = 0;
+    int like[MAXDEF], items[MAXDEF];
+    const double *part[MAXDEF], *add[MAXDEF];
+};
+
+// The in-launch hand-offs' give-up word (the unified launch, the bin co-run):
+// a word of pinned host memory that the kernels write through its device
+// mapping (pipe_giveup).  A step call that launched a hand-off kernel records
+// the event after it; the word is read once the event has completed -- at the
+// start of the next call, by the state readbacks (sampler_check_pipe) and
+// before a schedule's set-up clears it -- so a hand-off that gave up fails the
+// run loudly instead of leaving silently rejected trials.
+struct PipeStatus {
+    int *host = nullptr;       // pinned, mapped
+    int *dev = nullptr;        // its device address
+    hipEvent_t ev = nullptr;
+    bool pending = false;      // ev was recorded and the word not read since
+    void init();                                // allocated, read (waiting for ev) and zero
+    void post(hipStream_t stream);              // at the end of a step call
+    void post_nothrow(hipStream_t stream);      // on an error path: covers whatever the call launched before it
+    void check(bool wait);                      // fails if a hand-off gave up (without wait: only once ev has completed)
+    ~PipeStatus() {
+        if (host) (void)hipHostFree(host);
+        if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
+// Fast-step schedule: the unified step launch (schedunified.h).  One launch
+// per step holds step k's tails, step k + 1's pass and the Metropolis
+// workgroups that accept step k (waiting per tile on the tails: TailWait) and
+// propose step k + 1.
+struct UnifiedSteps {
+    int ready = 0;                    // W it is set up for (0: not yet, -W: not possible)
+    DevBuf S[2][2];                   // [parity][stage] the pass's raw sums (kind 1: bin-major, steptail.h)
+    DevBuf rowcal;                    // the chi^2 stage's calibrated partial rows (SmallGaussLaunch::row_cal)
+    int qf = -1, g = -1;              // the stage (0 / 1) of the quadratic form / of the chi^2
+    DevBuf cnt;                       // [tiles] TailWait::cnt
+    size_t cnt_bytes = 0;
+    unsigned epoch = 0;               // accepting launches of this call so far
+    unsigned epoch_g = 0;             // of them, those with the chi^2 as rows (not folded)
+    StepTailPlan plan[3];             // rows: propose + pass, tails + pass + accept/propose, tails + accept
+    size_t lds = 0;
+    bool binned_cache = false;        // cmbs_set_binned_cache: bin once per fast-step call
+    void invalidate() { ready = 0; }  // the counters and the epochs are set up afresh next time
+};
+
+// Fast-step schedule: the bin co-run (schedbin.h; a lone plik_lite
+// likelihood, no fused pass).  The proposing launch also bins every walker's
+// theory into raw sums (mh_bin_kernel), from which plik's deferred evaluation
+// continues.
+struct BinCorun {
+    int ready = 0;                    // W it is set up for (0: not yet)
+    DevBuf cal;                       // [2 halves][2 stages][ld] the calibration hand-off (DevCfg::calbuf)
+    unsigned epoch = 0;               // proposing launches so far (its parity: the half)
+    DevBuf S;                         // [wpad(W)][Np] raw bin sums (padding zero)
+    size_t lds = 0;                   // mh_bin_kernel's LDS
+    void invalidate() { ready = 0; }  // both halves re-uploaded as unset next time
+};
+
 }  // namespace cmamd
 
 struct cmbg;
@@ -243,11 +305,11 @@ struct cmbs {
     std::vector<int> sparse_likes;          // likelihood indices evaluated sparsely
     bool mask_on = false;                   // some likelihood can skip walkers (SetMask at add_likelihood)
     // deferred combines: the likelihoods that may defer (each with a workspace
-    // of its own, which must survive until the accepting mh_kernel), and how
-    // many the last evaluation left pending in dc.def_*
+    // of its own, which must survive until the accepting mh_kernel), and the
+    // ones the last evaluation left pending
     std::vector<int> defer_likes;
     cmamd::DevBuf like_ws[cmamd::MAXLIKE];
-    int pending_def = 0;
+    cmamd::PendingDeferred pending;
     // fused window pass (theorypass.h): plik_lite and a CMBlikes dataset that
     // read one theory buffer run their window stages as one pass; each then
     // continues from its own workspace (like_ws)
@@ -255,45 +317,17 @@ struct cmbs {
     int tp_like[2] = {-1, -1};               // [0] plik_lite (Delta rows), [1] CMBlikes (partial rows)
     cmamd::WinStage tp_stage[2];
     bool no_corun = false;                   // debug: the fused pass's tails as separate launches
-    // the bin co-run's calibration hand-off (mh_bin_kernel)
-    cmamd::DevBuf pipe_cal;                  // [2 halves][2 stages][ld] (DevCfg::calbuf)
-    unsigned pipe_epoch = 0;                 // proposing bin co-run launches so far (its parity: the half)
-    int pipe_ready = 0;                      // set up for this W (0: not yet)
-    // fast-step schedule: 3 the unified step launch (default, where it applies;
-    // else the bin co-run or the unpipelined steps), 0 unpipelined (debug /
-    // A/B: CMAMD_PIPE, cmamd_debug_pipeline)
-    int pipe_mode = 3;
-    cmamd::DevBuf tail_S[2][2];              // [parity][stage] the pass's raw sums (kind 1: bin-major, steptail.h)
-    cmamd::DevBuf tail_rowcal;               // the chi^2 stage's calibrated partial rows (SmallGaussLaunch::row_cal)
-    int tail_ready = 0;                      // W it is set up for (0: not yet, -W: not possible)
-    int tail_qf = -1, tail_g = -1;           // the stage (0 / 1) of the quadratic form / of the chi^2
-    // unified step launches: one launch per step holds step k's
-    // tails, step k + 1's pass and the Metropolis workgroups that accept step k
-    // (waiting per tile on the tails: TailWait) and propose step k + 1
-    cmamd::DevBuf tail_cnt;                  // [tiles] TailWait::cnt
-    size_t tail_cnt_bytes = 0;
-    unsigned tail_epoch = 0;
-    unsigned tail_epoch_g = 0;               // accepting unified launches with the chi^2 as rows (not folded)
-    cmamd::StepTailPlan uni_plan[3];         // rows: propose + pass, tails + pass + accept/propose, tails + accept
-    size_t uni_lds = 0;
-    int tail_nosignal = 0;                   // debug (cmamd_debug_tail_nosignal)
-    bool binned_cache = false;               // cmbs_set_binned_cache: bin once per fast-step call
-    // a pipelined hand-off that gave up (unified launch, bin co-run): the device word, its
-    // pinned copy taken at the end of each step call, checked at the next
-    int *pipe_status_host = nullptr;         // pinned, mapped (pipe_status_init)
-    int *pipe_status_dev = nullptr;          // its device address
-    hipEvent_t pipe_ev = nullptr;
-    bool pipe_ev_pending = false;
-    // bin co-run (a lone plik_lite likelihood, no fused pass): the proposing
-    // launch also bins every walker's theory into raw sums (mh_bin_kernel);
-    // plik's deferred evaluation continues from them (Like::deferred_from_sums)
-    cmamd::DevBuf bin_S;                     // [wpad(W)][Np] raw bin sums (padding zero)
-    size_t bin_lds = 0;                      // mh_bin_kernel's LDS
+    // fast-step schedules (sampler_step): 3 the unified step launch where it
+    // applies, else the bin co-run, else the unpipelined steps (default);
+    // 0 unpipelined (debug / A/B: CMAMD_PIPE, cmamd_debug_pipeline)
+    int sched_mode = 3;
+    cmamd::UnifiedSteps unified;
+    cmamd::BinCorun bin;
+    cmamd::PipeStatus pipe_status;           // both schedules' hand-offs
+    int handoff_nosignal = 0;                // debug: neither schedule's producers signal (cmamd_debug_tail_nosignal)
     int tp_why = 0;                          // set-up progress when no pass was built (debug)
     bool lean_off = false;                   // debug: the generic chain where the lean one applies (cmamd_debug_lean)
     ~cmbs() {
-        if (pipe_status_host) (void)hipHostFree(pipe_status_host);
-        if (pipe_ev) (void)hipEventDestroy(pipe_ev);
         for (auto &st : streams)
             if (st) (void)hipStreamDestroy(st);
         for (auto &e : events)

@@ -18,16 +18,17 @@
 // independent coalesced loads, runs the chain out of LDS and writes back.
 //
 // This file holds every kernel entry point of the chain, then the host side:
-// set-up and the fast-step schedules.  The device bodies are
+// set-up, the Metropolis launch and cmbs_step.  The device bodies are
 // headers included inside namespace cmamd, in this order: mhrng.h (RANMAR),
 // mhpropose.h (walker view, proposer, target), mhstage.h (LDS staging),
 // mhwait.h (the unified launch's arrival and wait), mhlean.h and mhbody.h (the
 // lean and the general chain), mhstep.h (the unified launch's roles), mhrot.h
-// (deferred rotations), mhdrag.h (fast dragging).  Two host-side headers
+// (deferred rotations), mhdrag.h (fast dragging).  Four host-side headers
 // follow in the same way: likeeval.h (the likelihoods' evaluation at a set of
-// points) and slowstep.h (cmbs_step_theory, cmbs_step_drag and
-// cmbs_refresh_theory).  The history statistics are history.hip, the state
-// image state.hip.
+// points), schedbin.h and schedunified.h (the two pipelined fast-step
+// schedules, each with its set-up, launches and run) and slowstep.h
+// (cmbs_step_theory, cmbs_step_drag and cmbs_refresh_theory).  The history
+// statistics are history.hip, the state image state.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -336,10 +337,9 @@ static void set_mh_lds(cmbs *s) {
         s->itmp_g.alloc((size_t)std::max(1, s->all_n) * d.ld * 4);
         d.itmp_g = s->itmp_g.as<int>();
     }
-    const int lds = (int)s->mh_lds;
-    HIP_CHECK(hipFuncSetAttribute((const void *)mh_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_CHECK(hipFuncSetAttribute((const void *)mh_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    HIP_CHECK(hipFuncSetAttribute((const void *)mh_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    for (const void *k : {(const void *)mh_kernel<true, true>, (const void *)mh_kernel<true, false>,
+                          (const void *)mh_kernel<false, true>})
+        HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->mh_lds));
 }
 
 static void upload_tables(cmbs *s) {
@@ -428,7 +428,6 @@ void sampler_create(cmbs *s, const cmbs_config_t *cfg) {
     d.max_blk = 1;
     for (int bn : s->blk_n) d.max_blk = std::max(d.max_blk, bn);
     d.rot_defer = d.max_blk >= ROT_DEFER_MIN ? 1 : 0;
-    d.bin_on = 0;
 
     // ---- shared tables
     TabLayout &tl = d.tl;
@@ -524,7 +523,6 @@ void sampler_create(cmbs *s, const cmbs_config_t *cfg) {
         d.pre_blk = (fb.size() == 1 && s->blk_n[fb[0]] >= 2) ? fb[0] : -1;
         d.pre_off = d.pre_blk >= 0 ? s->blk_R_off[d.pre_blk] : 0;
         d.pre_n = d.pre_blk >= 0 ? s->blk_n[d.pre_blk] : 0;
-        d.pre_lp = -1;
     }
     HIP_CHECK(hipFuncSetAttribute((const void *)rot_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)(ROT_WAVES * sizeof(RotLds))));
@@ -622,6 +620,13 @@ void sampler_set_test_gaussian(cmbs *s, const double *cov, const double *center)
 
 static void set_change_mask(cmbs *s);
 
+// the pipelined fast-step schedules' set-up no longer holds (likelihoods
+// changed, or a hand-off gave up): each sets up afresh at its next run
+static void invalidate_schedules(cmbs *s) {
+    s->unified.invalidate();
+    s->bin.invalidate();
+}
+
 // Segment starts (absolute l, even) about TP_MAXL apart over [lo, hi] at which
 // none of the bins [b.first, b.second] is split.
 static std::vector<int> bin_safe_cuts(const std::vector<std::pair<int, int>> &bins, int lo, int hi, int L) {
@@ -653,8 +658,7 @@ static std::vector<int> bin_safe_cuts(const std::vector<std::pair<int, int>> &bi
 static void setup_fusion(cmbs *s) {
     s->tpass.reset();
     s->tp_like[0] = s->tp_like[1] = -1;
-    s->pipe_ready = 0;
-    s->tail_ready = 0;
+    invalidate_schedules(s);
     const int nl = (int)s->likes.size();
     auto sparse = [&](int i) {
         for (int q : s->sparse_likes)
@@ -803,8 +807,7 @@ void sampler_add_derived_likelihood(cmbs *s, cmbg *g) {
     s->dc.like_nuis[r] = nullptr;
     set_change_mask(s);
     s->drv_cur = false;
-    s->tail_ready = 0;
-    s->pipe_ready = 0;
+    invalidate_schedules(s);
     s->drag_dd.release();   // the drag's scratch rows follow the number of term rows
 }
 
@@ -921,99 +924,51 @@ static bool rot_may_pend(cmbs *s, int fast_only, int g0) {
 
 void rot_schedule_unknown(cmbs *s) { std::fill(s->rot_lp.begin(), s->rot_lp.end(), -1); }
 
-// The in-launch hand-offs' give-up word (the unified launch, the bin co-run):
-// a word of pinned host memory that the kernels write through its device
-// mapping (pipe_giveup); zeroed here, checked once the step call's event has
-// completed -- at the start of the next call and by the state readbacks
-// (sampler_check_pipe) -- so a hand-off that gave up fails the run loudly
-// instead of leaving silently rejected trials.
-static void pipe_status_init(cmbs *s) {
-    if (!s->pipe_status_host) {
-        HIP_CHECK(hipHostMalloc((void **)&s->pipe_status_host, 64, hipHostMallocMapped | hipHostMallocCoherent));
-        HIP_CHECK(hipHostGetDevicePointer((void **)&s->pipe_status_dev, s->pipe_status_host, 0));
-        HIP_CHECK(hipEventCreateWithFlags(&s->pipe_ev, hipEventDisableTiming));
+void PipeStatus::init() {
+    if (!host) {
+        HIP_CHECK(hipHostMalloc((void **)&host, 64, hipHostMallocMapped | hipHostMallocCoherent));
+        HIP_CHECK(hipHostGetDevicePointer((void **)&dev, host, 0));
+        HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
-    // no kernel of an earlier call still writes it: every call that launched a
-    // hand-off kernel recorded pipe_ev after it (pipe_status_post, also on the
-    // error paths), so waiting on this sampler's event suffices -- other
-    // samplers' and the caller's work on the device are not waited for
-    if (s->pipe_ev_pending) HIP_CHECK(hipEventSynchronize(s->pipe_ev));
-    *reinterpret_cast<volatile int *>(s->pipe_status_host) = 0;
-    s->pipe_ev_pending = false;
+    // no kernel of an earlier call still writes the word once ev has completed:
+    // every call that launched a hand-off kernel recorded it afterwards (post,
+    // also on the error paths), so waiting on this sampler's event suffices --
+    // other samplers' and the caller's work on the device are not waited for.
+    // A give-up that call left is raised here, not cleared unread
+    check(true);
+    *reinterpret_cast<volatile int *>(host) = 0;
 }
 
-static void pipe_status_post(cmbs *s, hipStream_t stream) {
-    HIP_CHECK(hipEventRecord(s->pipe_ev, stream));
-    s->pipe_ev_pending = true;
+void PipeStatus::post(hipStream_t stream) {
+    HIP_CHECK(hipEventRecord(ev, stream));
+    pending = true;
 }
 
-// on an error path: the event covers whatever this call launched before it
-static void pipe_status_post_nothrow(cmbs *s, hipStream_t stream) {
-    if (s->pipe_ev && hipEventRecord(s->pipe_ev, stream) == hipSuccess) s->pipe_ev_pending = true;
+void PipeStatus::post_nothrow(hipStream_t stream) {
+    if (ev && hipEventRecord(ev, stream) == hipSuccess) pending = true;
 }
 
-void sampler_check_pipe(cmbs *s, bool wait) {
-    if (!s->pipe_ev_pending) return;
-    if (wait) HIP_CHECK(hipEventSynchronize(s->pipe_ev));
-    const hipError_t q = hipEventQuery(s->pipe_ev);
+void PipeStatus::check(bool wait) {
+    if (!pending) return;
+    if (wait) HIP_CHECK(hipEventSynchronize(ev));
+    const hipError_t q = hipEventQuery(ev);
     if (q == hipErrorNotReady) return;   // checked at a later call
     HIP_CHECK(q);
-    s->pipe_ev_pending = false;
-    if (*reinterpret_cast<volatile int *>(s->pipe_status_host) & CMBL_STATUS_PIPE_WAIT) {
-        *reinterpret_cast<volatile int *>(s->pipe_status_host) = 0;
-        s->tail_ready = 0;
-        s->pipe_ready = 0;
+    pending = false;
+    if (*reinterpret_cast<volatile int *>(host) & CMBL_STATUS_PIPE_WAIT) {
+        *reinterpret_cast<volatile int *>(host) = 0;
         fail(CMBL_ERR_NUMERIC, "a pipelined step's in-launch hand-off gave up waiting (CMBL_STATUS_PIPE_WAIT): "
                                "the walkers' last steps are invalid");
     }
 }
 
-// Whether this run of fast steps can take the bin co-run: one likelihood,
-// plik_lite, deferred (its quadratic form's combine in the next mh launch),
-// no fused pass, one walker group, no change mask.  Allocates the raw sums and
-// sets up the calibration hand-off (as pipe_setup).
-static bool bin_setup(cmbs *s, int fast_only, PlikBinArgs &pb) {
-    // (mode 3 needs the fused pass, so it falls back here with plik_lite alone)
-    if (s->pipe_mode == 0 || !fast_only || s->tpass || s->n_groups != 1 || s->mask_on ||
-        s->likes.size() != 1 || !s->dlikes.empty() || !is_deferred(s, 0))
-        return false;
-    const LikeSlot &L = s->likes[0];
-    WinStage st;
-    if (!L.like->like->bin_args(pb, L.th.dl, L.th.ld_field, L.th.ld_walker) || !L.like->like->window_stage(st) ||
-        st.cal_index < 0)
-        return false;
-    const size_t need = (size_t)QuadForm::wpad(s->W) * pb.Np * 8;
-    if (s->bin_S.bytes < need) {
-        s->bin_S.alloc(need);
-        HIP_CHECK(hipMemset(s->bin_S.p, 0, need));
+void sampler_check_pipe(cmbs *s, bool wait) {
+    try {
+        s->pipe_status.check(wait);
+    } catch (...) {
+        invalidate_schedules(s);
+        throw;
     }
-    for (int f = 0; f < 3; f++)
-        if (pb.fr.b1[f] - pb.fr.b0[f] > 2 * MH_THREADS) return false;   // mh_bin_kernel: two bins a thread
-    s->bin_lds = std::max(s->mh_lds, (size_t)pb.lds_doubles * 8);
-    if (s->bin_lds > 160 * 1024) return false;
-    HIP_CHECK(hipFuncSetAttribute((const void *)mh_bin_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)s->bin_lds));
-    HIP_CHECK(hipFuncSetAttribute((const void *)mh_bin_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)s->bin_lds));
-    if (s->pipe_ready == s->W) return true;
-    pipe_status_init(s);
-    {   // both halves unset: the first launch publishes into half 1, resets half 0
-        const std::vector<unsigned long long> unset((size_t)4 * s->dc.ld, TP_PIPE_UNSET);
-        s->pipe_cal.alloc(unset.size() * 8);
-        s->pipe_cal.upload(unset.data(), unset.size() * 8);
-    }
-    s->pipe_epoch = 0;
-    s->pipe_ready = s->W;
-    return true;
-}
-
-// plik's deferred quadratic form over the Delta rows the bin co-run (and
-// rot_kernel) formed; its combine runs in the next Metropolis launch
-static void launch_bin_qf(cmbs *s, hipStream_t stream) {
-    Like &Q = *s->likes[0].like->like;
-    const QFDeferred d = Q.after_window(s->W, s->dc.like_nuis[0], std::max(1, Q.n_nuis), nullptr, s->like_ws[0].p,
-                                        stream, true);
-    record_deferred(s, 0, d);
 }
 
 // The lean chain's LDS (mhlean.h's carve)
@@ -1050,79 +1005,62 @@ static LeanCfg lean_cfg(const cmbs *s, int fast_only, bool masked) {
     return L;
 }
 
-static void launch_mh(cmbs *s, bool accept, bool propose, int fast_only, const HistRow &row, hipStream_t stream,
-                      int g0, int g1, bool masked = false, const PlikBinArgs *bin = nullptr) {
-    const dim3 g((g1 - g0 + MB - 1) / MB), b(MH_THREADS);
-    const int blk0 = g0 / MB;
-    const size_t lds = s->mh_lds;
+// The DevCfg of one launch: the sampler's, with every per-launch field at its
+// neutral value except the deferred combines the last evaluation left
+// pending, which it takes over.  The launchers set what they use.
+static DevCfg launch_cfg(cmbs *s, int fast_only, bool masked) {
     DevCfg dc = s->dc;
     dc.mask_on = masked ? 1 : 0;
     dc.lean = lean_cfg(s, fast_only, masked);
-    if (s->pending_def && !accept) fail(CMBL_ERR_ARG, "internal: deferred likelihoods without an accepting step");
-    dc.pre_lp = -1;   // the single deferred block's loop index before this launch's proposals (rot_may_pend)
-    if (propose && fast_only && s->dc.rot_defer && s->rot_fast_n > 0 && dc.pre_blk >= 0 && s->rot_lp[g0 / 64] >= 0)
+    dc.pre_lp = -1;
+    dc.rot_par = 0;
+    dc.pub_on = 0;
+    dc.bin_on = 0;
+    PendingDeferred &pd = s->pending;
+    dc.n_def = pd.n;
+    std::copy(pd.like, pd.like + pd.n, dc.def_like);
+    std::copy(pd.items, pd.items + pd.n, dc.def_items);
+    std::copy(pd.part, pd.part + pd.n, dc.def_part);
+    std::copy(pd.add, pd.add + pd.n, dc.def_add);
+    pd.n = 0;
+    return dc;
+}
+
+// The rotation schedule's part of a launch over the walker range from g0:
+// whether rot_kernel follows it (launch_rot), and then its rotation list
+static bool rot_schedule(cmbs *s, DevCfg &dc, bool propose, int fast_only, int g0) {
+    // the single deferred block's loop index before this launch's proposals (rot_may_pend)
+    if (propose && fast_only && dc.rot_defer && s->rot_fast_n > 0 && dc.pre_blk >= 0 && s->rot_lp[g0 / 64] >= 0)
         dc.pre_lp = s->rot_lp[g0 / 64];
     const bool rot = propose && rot_may_pend(s, fast_only, g0);
     if (rot) {                       // alternate the two rotation-list counters of this walker range
         dc.rot_par = s->rot_par[g0 / 64];
         s->rot_par[g0 / 64] ^= 1;
     }
-    dc.n_def = s->pending_def;
-    s->pending_def = 0;
-    dc.pub_on = 0;
-    if (bin) {   // mh_bin_kernel: the proposing launch bins the theory beside the Metropolis workgroups
-        if (!propose || g0 != 0 || g1 != s->W) fail(CMBL_ERR_ARG, "internal: bin co-run launch");
-        Like &Q = *s->likes[0].like->like;
-        WinStage st;
-        Q.window_stage(st);
-        dc.pub_on = s->tail_nosignal ? 0 : 1;   // debug: never publish (the give-up test)
-        dc.pub_pcal[0] = s->likes[0].nidx[st.cal_index];
-        dc.pub_pcal[1] = -1;
-        const unsigned e = s->pipe_epoch + 1;   // this launch's half e % 2; it resets the other for the next
-        dc.calbuf = s->pipe_cal.as<double>() + (size_t)(e % 2) * 2 * dc.ld;
-        dc.calbuf_next = s->pipe_cal.as<double>() + (size_t)((e + 1) % 2) * 2 * dc.ld;
-        dc.bin_on = 1;
-        dc.bin_nused = bin->nused;
-        dc.bin_Np = bin->Np;
-        dc.bin_cal = st.cal_index;
-        dc.bin_S = s->bin_S.as<double>();
-        dc.bin_X = bin->X;
-        dc.bin_delta = Q.window_out(s->like_ws[0].p, s->W);
-        const int nmh = (int)g.x, nmh_pad = (nmh + 7) / 8 * 8;
-        const dim3 gb(nmh_pad + s->W);
-        try {
-            timed_launch("mh_bin_kernel", stream, [&](hipEvent_t e0, hipEvent_t e1) {
-                if (accept)
-                    hipExtLaunchKernelGGL(mh_bin_kernel<true>, gb, b, s->bin_lds, stream, e0, e1, 0, dc, fast_only,
-                                          row.p, row.t, nmh, nmh_pad, *bin, s->pipe_status_dev);
-                else
-                    hipExtLaunchKernelGGL(mh_bin_kernel<false>, gb, b, s->bin_lds, stream, e0, e1, 0, dc, fast_only,
-                                          row.p, row.t, nmh, nmh_pad, *bin, s->pipe_status_dev);
-            });
-            HIP_CHECK(hipGetLastError());
-        } catch (...) {
-            s->pipe_ready = 0;   // both halves re-uploaded as unset next time
-            pipe_status_post_nothrow(s, stream);
-            throw;
-        }
-        s->pipe_epoch = e;
-    } else
-    timed_launch("mh_kernel", stream, [&](hipEvent_t e0, hipEvent_t e1) {
-        if (accept && propose)
-            hipExtLaunchKernelGGL(mh_kernel<true, true>, g, b, lds, stream, e0, e1, 0, dc, fast_only, row.p, row.t, blk0);
-        else if (accept)
-            hipExtLaunchKernelGGL(mh_kernel<true, false>, g, b, lds, stream, e0, e1, 0, dc, fast_only, row.p, row.t, blk0);
-        else
-            hipExtLaunchKernelGGL(mh_kernel<false, true>, g, b, lds, stream, e0, e1, 0, dc, fast_only, row.p, row.t, blk0);
+    return rot;
+}
+
+// the walkers of [g0, g1) whose proposal waits on a new rotation
+static void launch_rot(const DevCfg &dc, hipStream_t stream, int g0, int g1) {
+    timed_launch("rot_kernel", stream, [&](hipEvent_t e0, hipEvent_t e1) {
+        hipExtLaunchKernelGGL(rot_kernel, dim3((g1 - g0 + ROT_WAVES - 1) / ROT_WAVES), dim3(64 * ROT_WAVES),
+                              ROT_WAVES * sizeof(RotLds), stream, e0, e1, 0, dc, g0);
     });
-    if (rot) {                       // the walkers whose proposal waits on a new rotation
-        HIP_CHECK(hipGetLastError());
-        timed_launch("rot_kernel", stream, [&](hipEvent_t e0, hipEvent_t e1) {
-            hipExtLaunchKernelGGL(rot_kernel, dim3((g1 - g0 + ROT_WAVES - 1) / ROT_WAVES), dim3(64 * ROT_WAVES),
-                                  ROT_WAVES * sizeof(RotLds), stream, e0, e1, 0, dc, g0);
-        });
-    }
     HIP_CHECK(hipGetLastError());
+}
+
+static void launch_mh(cmbs *s, bool accept, bool propose, int fast_only, const HistRow &row, hipStream_t stream,
+                      int g0, int g1, bool masked = false) {
+    const dim3 g((g1 - g0 + MB - 1) / MB), b(MH_THREADS);
+    if (s->pending.n && !accept) fail(CMBL_ERR_ARG, "internal: deferred likelihoods without an accepting step");
+    DevCfg dc = launch_cfg(s, fast_only, masked);
+    const bool rot = rot_schedule(s, dc, propose, fast_only, g0);
+    timed_launch("mh_kernel", stream, [&](hipEvent_t e0, hipEvent_t e1) {
+        const auto k = !accept ? mh_kernel<false, true> : propose ? mh_kernel<true, true> : mh_kernel<true, false>;
+        hipExtLaunchKernelGGL(k, g, b, s->mh_lds, stream, e0, e1, 0, dc, fast_only, row.p, row.t, g0 / MB);
+    });
+    HIP_CHECK(hipGetLastError());
+    if (rot) launch_rot(dc, stream, g0, g1);
 }
 
 void sampler_set_start(cmbs *s, const double *P0, hipStream_t stream) {
@@ -1151,266 +1089,22 @@ static void check_theory_fresh(const cmbs *s) {
                            "theory at the restored points with cmbs_refresh_theory before stepping");
 }
 
-// The unified pipelined fast steps (mh_step_kernel, steptail.h): whether this run of fast steps
-// can take them -- the fused pass's vectorised form over one walker group, no
-// change mask, no rotations left to rot_kernel, and its two stages a deferred
-// quadratic form (plik_lite: every row calibrated) and a small chi^2 another
-// launch can carry (Planck lensing).  Sets up the raw-sum buffers once per W.
-static bool tail_setup(cmbs *s, int fast_only) {
-    // (the unified launch carries the fused pair alone: with a third likelihood the
-    // run takes the unpipelined steps, whose eval_likes runs every likelihood; BASELINE
-    // configs[2] with a lowl term would be such a run -- clik is absent, so none exists here)
-    if (s->pipe_mode == 0 || !fast_only || !s->tpass || s->n_groups != 1 || s->mask_on ||
-        (s->dc.rot_defer && s->rot_fast_any) || s->likes.size() != 2 || !s->dlikes.empty())
-        return false;
-    {
-        const TheoryView &P = s->likes[s->tp_like[0]].th;
-        if (!s->tpass->vec_ok(P.dl, P.ld_field, P.ld_walker)) return false;
+#include "schedbin.h"
+#include "schedunified.h"
+
+// propose(1) | likes | accept(1)+propose(2) | likes | ... | likes | accept(n)
+static void run_plain(cmbs *s, int n_steps, int fast_only, hipStream_t stream) {
+    for (int k = 0; k <= n_steps; k++) {
+        launch_mh(s, k > 0, k < n_steps, fast_only, k > 0 ? next_hist(s) : HistRow{}, stream, 0, s->W, s->mask_on);
+        if (k < n_steps) eval_trial_likes(s, stream, true);
     }
-    if (s->tail_ready == s->W) return true;
-    if (s->tail_ready == -s->W) return false;
-    s->tail_ready = -s->W;
-    s->tail_qf = s->tail_g = -1;
-    for (int k = 0; k < 2; k++) {
-        const int i = s->tp_like[k];
-        Like &L = *s->likes[i].like->like;
-        const WinStage &st = s->tp_stage[k];
-        QFSource src;
-        if (st.kind == 1 && is_deferred(s, (size_t)i) && L.qf_source(src, s->W, s->like_ws[i].p)) {
-            bool all_cal = st.cal_index >= 0;
-            for (const WinCol &c : st.cols) all_cal = all_cal && c.cal;
-            if (all_cal && st.ld == src.Np) s->tail_qf = k;
-        }
-        SmallGaussLaunch g{};
-        if (st.kind == 0 && L.corun_small(g, s->W, s->dc.like_nuis[i], L.n_nuis,
-                                          s->like_terms.as<double>() + (size_t)i * s->dc.ld, s->like_ws[i].p))
-            s->tail_g = k;
-    }
-    if (s->tail_qf < 0 || s->tail_g < 0 || s->tail_qf == s->tail_g) return false;
-    const size_t Wp = (size_t)QuadForm::wpad(s->W);
-    int rows = 0;
-    for (const WinCol &c : s->tp_stage[s->tail_g].cols) rows = std::max(rows, c.row + 1);
-    const size_t bytes[2] = {Wp * (size_t)s->tp_stage[s->tail_qf].ld * 8, (size_t)rows * s->W * 8};
-    for (int p = 0; p < 2; p++)
-        for (int k = 0; k < 2; k++) {
-            const size_t b = bytes[k == s->tail_qf ? 0 : 1];
-            s->tail_S[p][k].alloc(b);
-            HIP_CHECK(hipMemset(s->tail_S[p][k].p, 0, b));   // padding bins / walkers stay 0
-        }
-    std::vector<unsigned char> rc((size_t)rows + 16, 0);
-    for (const WinCol &c : s->tp_stage[s->tail_g].cols) rc[c.row] = c.cal ? 1 : 0;
-    s->tail_rowcal.alloc(rc.size());
-    s->tail_rowcal.upload(rc.data(), rc.size());
-    // the unified launch's arrival counters (from 0, epoch 0) and its LDS
-    s->tail_cnt_bytes = (Wp / QF_TILE * TW_PAD * 4 + 15) & ~(size_t)15;   // a multiple of 16 from the start
-    s->tail_cnt.alloc(s->tail_cnt_bytes);
-    HIP_CHECK(hipMemset(s->tail_cnt.p, 0, s->tail_cnt_bytes));
-    s->tail_epoch = 0;
-    s->tail_epoch_g = 0;
-    pipe_status_init(s);
-    {
-        const int gi = s->tp_like[s->tail_g];
-        Like &G = *s->likes[gi].like->like;
-        SmallGaussLaunch g{};
-        G.corun_small(g, s->W, s->dc.like_nuis[gi], G.n_nuis, s->like_terms.as<double>() + (size_t)gi * s->dc.ld,
-                      s->like_ws[gi].p);
-        s->uni_lds = std::max({s->mh_lds, (size_t)QFS_LDS_DOUBLES * 8, (size_t)tp_vec_lds_bytes<2>(),
-                               (size_t)small_gauss_lds_doubles<UNI_WT>(g.d.nX) * 8,
-                               (size_t)small_gauss_lds_doubles<MB>(g.d.nX) * 8});
-        for (const void *k : {(const void *)mh_step_kernel<false, true>, (const void *)mh_step_kernel<true, true>,
-                              (const void *)mh_step_kernel<true, false>, (const void *)mh_tail_kernel<true, true>,
-                              (const void *)mh_tail_kernel<true, false>})
-            HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->uni_lds));
-    }
-    for (auto &pl : s->uni_plan) pl.key[0] = -1;
-    s->tail_ready = s->W;
-    return true;
 }
 
-// One step tail: the quadratic form and the chi^2 of the step whose raw sums
-// are in half rd (rd < 0: none), and the pass storing the next step's raw sums
-// into half wr (wr < 0: none).
-static StepTail make_tail(cmbs *s, int rd, int wr) {
-    StepTail t;
-    const int W = s->W;
-    t.W = W;
-    if (rd >= 0) {
-        const int qi = s->tp_like[s->tail_qf], gi = s->tp_like[s->tail_g];
-        Like &Q = *s->likes[qi].like->like;
-        Like &G = *s->likes[gi].like->like;
-        if (!Q.qf_source(t.q.src, W, s->like_ws[qi].p)) fail(CMBL_ERR_ARG, "internal: step tail quadratic form");
-        t.q.S = s->tail_S[rd][s->tail_qf].as<double>();
-        t.q.nuis = s->dc.like_nuis[qi];
-        t.q.ld_nuis = std::max(1, Q.n_nuis);
-        t.q.cal_index = s->tp_stage[s->tail_qf].cal_index;
-        t.q.W = W;
-        t.q.Wp = QuadForm::wpad(W);
-        t.nq = t.q.src.n_items * (QuadForm::wpad(W) / QF_TILE);
-        if (!G.corun_small(t.g, W, s->dc.like_nuis[gi], G.n_nuis, s->like_terms.as<double>() + (size_t)gi * s->dc.ld,
-                           s->like_ws[gi].p))
-            fail(CMBL_ERR_ARG, "internal: step tail chi^2");
-        t.g.partial = s->tail_S[rd][s->tail_g].as<double>();
-        t.g.row_cal = s->tail_rowcal.as<unsigned char>();
-        t.g.stage_cal = s->tp_stage[s->tail_g].cal_index;
-        t.ng = (W + UNI_WT - 1) / UNI_WT;
-        // the chi^2 folded into the Metropolis workgroups: bit-identical while its
-        // 16-walker body's thread groups (256 / 16) cover the bandpowers
-        // (middle launches only: in the accept-only launch that ends a call the
-        // chi^2 would sit on the chain's critical path, 21.5 against 23.3 us)
-        t.fold_g = (wr >= 0 && t.g.d.nX <= MH_THREADS / MB) ? 1 : 0;
-        if (t.fold_g) t.ng = 0;
-    }
-    if (wr >= 0) {
-        TPOut o[2];
-        for (int k = 0; k < 2; k++) {
-            const int i = s->tp_like[k];
-            const WinStage &st = s->tp_stage[k];
-            Like &L = *s->likes[i].like->like;
-            // (the raw pass stores the kind-1 stage bin-major, steptail.h: its row stride is wpad(W))
-            o[k] = TPOut{st.kind, st.cal_index, st.kind == 1 ? QuadForm::wpad(W) : st.ld, 0,
-                         s->tail_S[wr][k].as<double>(), st.X, s->dc.like_nuis[i], (long long)std::max(1, L.n_nuis)};
-        }
-        t.tp = s->tpass->dev_args(o, W);
-        const TheoryView &P = s->likes[s->tp_like[0]].th;
-        t.dl = P.dl;
-        t.ld_field = P.ld_field;
-        t.ld_walker = P.ld_walker;
-        t.np = s->tpass->n_blocks();
-    }
-    return t;
-}
-
-// One unified step launch (pipe_mode 3, mh_step_kernel): the tails of the
-// step whose raw sums are in half rd (rd < 0: none), the pass into half wr
-// (wr < 0: none), and the Metropolis workgroups accepting that step (when
-// rd >= 0) and proposing the next (propose).
-static void launch_unified(cmbs *s, hipStream_t stream, bool propose, int rd, int wr, const HistRow &row,
-                           int fast_only) {
-    const bool accept = rd >= 0;
-    StepTail t = make_tail(s, rd, wr);
-    DevCfg dc = s->dc;
-    dc.mask_on = 0;
-    dc.lean = lean_cfg(s, fast_only, false);
-    dc.pub_on = 0;
-    dc.n_def = 0;
-    s->pending_def = 0;
-    if (accept) {   // plik's combine from this launch's partials (QFDeferred)
-        dc.n_def = 1;
-        dc.def_like[0] = s->tp_like[s->tail_qf];
-        dc.def_items[0] = t.q.src.n_items;
-        dc.def_part[0] = t.q.src.partial;
-        dc.def_add[0] = nullptr;
-    }
-    const int ng_rows = t.ng;
-    TailWait tw{};
-    tw.cnt = s->tail_cnt.as<unsigned int>();
-    tw.epoch = s->tail_epoch + (accept ? 1u : 0u);
-    tw.epoch_g = s->tail_epoch_g + ((accept && !t.fold_g) ? 1u : 0u);
-    tw.nq_items = t.q.src.n_items;
-    tw.ng = accept ? (s->W + UNI_WT - 1) / UNI_WT : 0;   // an unfolded launch's chi^2 workgroups (the target's
-    tw.gwt = UNI_WT;                                      // per-tile count for the epoch_g launches)
-    tw.status = s->pipe_status_dev;
-    tw.nosignal = s->tail_nosignal;
-    tw.stamp_slot = propose ? 0 : 1;
-    tw.ntiles = (int)(s->tail_cnt_bytes / 4);
-    const int nmh = (s->W + MB - 1) / MB;
-    const int v = accept ? (propose ? 1 : 2) : 0;
-    StepTailPlan &pl = s->uni_plan[v];
-    if (pl.key[0] != t.nq || pl.key[1] != ng_rows || pl.key[2] != t.np) {
-        const std::vector<int2> rows = tail_rows(t.nq, ng_rows, t.np, nmh);
-        pl.d_rows.alloc(rows.size() * sizeof(int2));
-        pl.d_rows.upload(rows.data(), rows.size() * sizeof(int2));
-        pl.nrows = (int)rows.size();
-        pl.key[0] = t.nq;
-        pl.key[1] = ng_rows;
-        pl.key[2] = t.np;
-    }
-    const dim3 grid((unsigned)pl.nrows * 8), b(MH_THREADS);
-    const int2 *rows = pl.d_rows.as<int2>();
-    static const char *names[3] = {"mh_step_first", "mh_step_kernel", "mh_step_last"};
-    static const char *cnames[3] = {"mh_step_first", "mh_tail_kernel", "mh_tail_last"};
-    const bool cached = s->binned_cache && accept && wr < 0 && rd == 0;   // the binned-cache steps (no pass)
-    try {
-        timed_launch(cached ? cnames[v] : names[v], stream, [&](hipEvent_t e0, hipEvent_t e1) {
-            if (cached && v == 1)
-                hipExtLaunchKernelGGL(mh_tail_kernel<true, true>, grid, b, s->uni_lds, stream, e0, e1, 0, dc,
-                                      fast_only, row.p, row.t, t, rows, tw, nmh);
-            else if (cached && v == 2)
-                hipExtLaunchKernelGGL(mh_tail_kernel<true, false>, grid, b, s->uni_lds, stream, e0, e1, 0, dc,
-                                      fast_only, row.p, row.t, t, rows, tw, nmh);
-            else if (v == 0)
-                hipExtLaunchKernelGGL(mh_step_kernel<false, true>, grid, b, s->uni_lds, stream, e0, e1, 0, dc,
-                                      fast_only, row.p, row.t, t, rows, tw, nmh);
-            else if (v == 1)
-                hipExtLaunchKernelGGL(mh_step_kernel<true, true>, grid, b, s->uni_lds, stream, e0, e1, 0, dc, fast_only,
-                                      row.p, row.t, t, rows, tw, nmh);
-            else
-                hipExtLaunchKernelGGL(mh_step_kernel<true, false>, grid, b, s->uni_lds, stream, e0, e1, 0, dc,
-                                      fast_only, row.p, row.t, t, rows, tw, nmh);
-        });
-        HIP_CHECK(hipGetLastError());
-    } catch (...) {
-        s->tail_ready = 0;   // the counters and the epoch are set up afresh next time
-        pipe_status_post_nothrow(s, stream);
-        throw;
-    }
-    if (accept) s->tail_epoch++;
-    if (accept && !t.fold_g) s->tail_epoch_g++;
-}
-
-void sampler_step(cmbs *s, int n_steps, int fast_only, hipStream_t stream) {
-    if (!s->started) fail(CMBL_ERR_ARG, "cmbs_set_start must be called before cmbs_step");
-    check_theory_fresh(s);
-    if (fast_only && s->fast_n == 0) fail(CMBL_ERR_ARG, "no fast parameters");
-    if (!fast_only && s->slow_n > 0 && s->n_rows() > 0)
-        fail(CMBL_ERR_ARG, "slow proposals need the theory at the trial point: use cmbs_step_theory");
-    check_derived_calc(s, "cmbs_step");
-    if (n_steps <= 0) return;
-    derived_rows_current(s, stream);
-    // propose(1) | likes | accept(1)+propose(2) | likes | ... | likes | accept(n)
+// The same steps per walker group.  Groups are independent chains: fork from
+// the caller's stream, issue the step chain of every group breadth-first so
+// the queues interleave, join
+static void run_groups(cmbs *s, int n_steps, int fast_only, hipStream_t stream) {
     const int G = s->n_groups;
-    sampler_check_pipe(s);
-    if (G == 1 && tail_setup(s, fast_only)) {
-        // unified: propose(1) + pass(1) | tails(1) + pass(2) + accept(1) + propose(2) | ... |
-        // tails(n) + accept(n): one launch per step.  The arrival counters start from 0
-        // in every call (the first launch zeroes them; the epochs are counted within it)
-        s->tail_epoch = 0;
-        s->tail_epoch_g = 0;
-        launch_unified(s, stream, true, -1, 0, HistRow{}, fast_only);
-        if (s->binned_cache) {
-            // the theory is fixed within the call: every step's tails read the raw
-            // sums the first launch's pass wrote (half 0), and no launch re-bins
-            for (int k = 0; k < n_steps; k++)
-                launch_unified(s, stream, k + 1 < n_steps, 0, -1, next_hist(s), fast_only);
-        } else
-        for (int k = 0; k < n_steps; k++)
-            launch_unified(s, stream, k + 1 < n_steps, k % 2, k + 1 < n_steps ? (k + 1) % 2 : -1, next_hist(s),
-                           fast_only);
-        pipe_status_post(s, stream);
-        return;
-    }
-    PlikBinArgs pb;
-    if (G == 1 && bin_setup(s, fast_only, pb)) {
-        // bin co-run: propose(1) + bins(1) | [rotations] | quadform(1) | accept(1) + propose(2) + bins(2) |
-        // ... | quadform(n) | accept(n)
-        for (int k = 0; k < n_steps; k++) {
-            launch_mh(s, k > 0, true, fast_only, k > 0 ? next_hist(s) : HistRow{}, stream, 0, s->W, false, &pb);
-            launch_bin_qf(s, stream);
-        }
-        launch_mh(s, true, false, fast_only, next_hist(s), stream, 0, s->W, false);
-        pipe_status_post(s, stream);
-        return;
-    }
-    if (G == 1) {
-        for (int k = 0; k <= n_steps; k++) {
-            const HistRow row = k > 0 ? next_hist(s) : HistRow{};
-            launch_mh(s, k > 0, k < n_steps, fast_only, row, stream, 0, s->W, s->mask_on);
-            if (k < n_steps) eval_trial_likes(s, stream, true);
-        }
-        return;
-    }
-    // groups are independent chains: fork from the caller's stream, issue the
-    // step chain of every group breadth-first so the queues interleave, join
     HIP_CHECK(hipEventRecord(s->events[MAXGROUPS], stream));
     for (int g = 0; g < G; g++) HIP_CHECK(hipStreamWaitEvent(s->streams[g], s->events[MAXGROUPS], 0));
     // A fused pair (the window pass over one theory buffer) is evaluated for the
@@ -1432,6 +1126,24 @@ void sampler_step(cmbs *s, int n_steps, int fast_only, hipStream_t stream) {
         HIP_CHECK(hipEventRecord(s->events[g], s->streams[g]));
         HIP_CHECK(hipStreamWaitEvent(stream, s->events[g], 0));
     }
+}
+
+void sampler_step(cmbs *s, int n_steps, int fast_only, hipStream_t stream) {
+    if (!s->started) fail(CMBL_ERR_ARG, "cmbs_set_start must be called before cmbs_step");
+    check_theory_fresh(s);
+    if (fast_only && s->fast_n == 0) fail(CMBL_ERR_ARG, "no fast parameters");
+    if (!fast_only && s->slow_n > 0 && s->n_rows() > 0)
+        fail(CMBL_ERR_ARG, "slow proposals need the theory at the trial point: use cmbs_step_theory");
+    check_derived_calc(s, "cmbs_step");
+    if (n_steps <= 0) return;
+    derived_rows_current(s, stream);
+    sampler_check_pipe(s);
+    const int G = s->n_groups;
+    PlikBinArgs pb;
+    if (G == 1 && unified_setup(s, fast_only)) run_unified(s, n_steps, fast_only, stream);
+    else if (G == 1 && bin_setup(s, fast_only, pb)) run_bin_corun(s, n_steps, fast_only, pb, stream);
+    else if (G == 1) run_plain(s, n_steps, fast_only, stream);
+    else run_groups(s, n_steps, fast_only, stream);
 }
 
 #include "slowstep.h"
@@ -1504,7 +1216,7 @@ extern "C" int cmamd_debug_tail_rows(int nq, int ng, int np, int nm, int *out, i
 }
 extern "C" int cmamd_debug_pipeline(cmbs *s, int mode) {   // fast-step schedule (sampler_step): 0 unpipelined,
     if (!s || (mode != 0 && mode != 3)) return -1;   // 3 the unified launch (default), 0 unpipelined
-    s->pipe_mode = mode;
+    s->sched_mode = mode;
     return 0;
 }
 extern "C" int cmamd_debug_lean(cmbs *s, int on) {   // the lean chain where it applies (1, default) or mh_body (0)
@@ -1517,9 +1229,9 @@ extern "C" int cmamd_debug_corun(cmbs *s, int on) {     // the lensing chi^2 ins
     s->no_corun = !on;
     return 0;
 }
-extern "C" int cmamd_debug_tail_nosignal(cmbs *s, int on) {   // in-launch producers never arrive / publish (modes 1, 3)
+extern "C" int cmamd_debug_tail_nosignal(cmbs *s, int on) {   // in-launch producers never arrive / publish
     if (!s) return -1;
-    s->tail_nosignal = on;
+    s->handoff_nosignal = on;
     return 0;
 }
 extern "C" int cmamd_debug_drag_pair(cmbs *s, int on) {   // both drag evaluation sets in two launches
@@ -1533,9 +1245,9 @@ extern "C" int cmamd_debug_drag_hbm(cmbs *s, int on) {   // the drag stages on t
     return 0;
 }
 extern "C" int cmamd_debug_pipe_status(cmbs *s) {   // the give-up word (synchronises the device)
-    if (!s || !s->pipe_status_host) return -1;
+    if (!s || !s->pipe_status.host) return -1;
     if (hipDeviceSynchronize() != hipSuccess) return -1;
-    return *reinterpret_cast<volatile int *>(s->pipe_status_host);
+    return *reinterpret_cast<volatile int *>(s->pipe_status.host);
 }
-extern "C" int cmamd_debug_tail(const cmbs *s) { return s ? s->tail_ready : 0; }   // W of the step tails' set-up
+extern "C" int cmamd_debug_tail(const cmbs *s) { return s ? s->unified.ready : 0; }   // W of the step tails' set-up
 extern "C" int cmamd_debug_fused(const cmbs *s) { return !s ? 0 : s->tpass ? s->tpass->n_items() : -s->tp_why; }

@@ -22,7 +22,7 @@
 namespace cmamd {
 
 // The kind-1 stage's raw sums are stored bin-major, S[Np][Wp] with Wp =
-// QuadForm::wpad(W) (both halves of the sampler's tail_S): the pass's emit has
+// QuadForm::wpad(W) (both halves of the sampler's UnifiedSteps::S): the pass's emit has
 // 16 consecutive walkers on a wave's lanes, so each of its store instructions
 // writes whole 128-byte lines (4 bins x 16 walkers) instead of 64 eight-byte
 // pieces of 64 walker rows, and the quadratic form's lanes, 16 walkers wide as
