@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "jlamarge.h"
 #include "sampler.h"
 #include "theorycalc.h"
 
@@ -102,6 +103,7 @@ int cmbl_open(const char *tag, const char *dataset_path, const char *override_in
         if (t == "PLIK_LITE") h->like = cmamd::make_plik_lite(ini);
         else if (t == "SPTPOL_TEEE" || t == "SPTPOL_BB") h->like = cmamd::make_sptpol(ini, t);   // CMB.f90:86-91
         else if (t == "JLA") h->like = cmamd::make_jla(ini);   // JLALikelihood_Add (supernovae_JLA.f90:221-262)
+        else if (t == "JLA_MARGE") h->like = cmamd::make_jla_marge(ini);   // the same with JLA_marginalize = T (:235-252)
         else if (t == "WMAP")   // CMB.f90:75-84: needs the external WMAP likelihood library
             cmamd::fail(CMBL_ERR_UNSUPPORTED, "cmbl_open: dataset tag '%s' not supported", tag);
         else h->like = cmamd::make_cmblikes(ini, t);      // TCMBLikes, TBK_planck (BKPLANCK), TSmica_planck (SMICA)
@@ -128,6 +130,11 @@ int cmbl_info(const cmbl_t *h, int *n_nuis, int *cl_lmax, int *speed, const char
 }
 
 int cmbl_theory_len(const cmbl_t *h) { return h && h->like ? h->like->theory_len : 0; }
+
+int cmbl_jla_marge_info(const cmbl_t *h, int *n_grid, int *n_points, size_t *grid_bytes) {
+    if (!h || !h->like || !cmamd::jla_marge_info(h->like.get(), n_grid, n_points, grid_bytes)) return CMBL_ERR_ARG;
+    return CMBL_OK;
+}
 
 int cmbl_derived_info(const cmbl_t *h, int *n_derived, const char **derived_names) {
     if (!h || !h->like) return CMBL_ERR_ARG;

@@ -386,6 +386,7 @@ std::unique_ptr<Like> make_plik_lite(const Ini &ini);
 std::unique_ptr<Like> make_cmblikes(const Ini &ini, const std::string &tag);
 std::unique_ptr<Like> make_sptpol(const Ini &ini, const std::string &tag);   // SPTPOL_TEEE / SPTPOL_BB
 std::unique_ptr<Like> make_jla(const Ini &ini);                             // jla.hip
+std::unique_ptr<Like> make_jla_marge(const Ini &ini);                       // jlamarge.hip
 
 }  // namespace cmamd
 

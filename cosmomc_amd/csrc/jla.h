@@ -26,6 +26,7 @@ struct JlaData {
     std::vector<double> comp[JLA_NCOMP];
 };
 
-JlaData load_jla(const Ini &ini);
+// marginalised: the caller serves JLA_marginalize = T (jlamarge.hip); otherwise the key is refused
+JlaData load_jla(const Ini &ini, bool marginalised = false);
 
 }  // namespace cmamd

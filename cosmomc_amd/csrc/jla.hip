@@ -75,10 +75,11 @@ static std::vector<double> jla_read_cov(const std::string &path, int n) {
     return m;
 }
 
-JlaData load_jla(const Ini &ini) {
+JlaData load_jla(const Ini &ini, bool marginalised) {
     JlaData d;
-    if (jla_logical(ini, "JLA_marginalize", false))
-        fail(CMBL_ERR_UNSUPPORTED, "JLA: JLA_marginalize = T is not supported (alpha_JLA, beta_JLA are sampled)");
+    if (!marginalised && jla_logical(ini, "JLA_marginalize", false))
+        fail(CMBL_ERR_UNSUPPORTED, "JLA: JLA_marginalize = T is not supported under this tag (alpha_JLA, beta_JLA are "
+                                   "sampled); open the dataset with the tag JLA_MARGE");
     // has_absdist is read as a logical from the key absdist_file, and the file
     // name it would open is never assigned (:621, 654)
     if (jla_logical(ini, "absdist_file", false))

@@ -5,6 +5,12 @@
 of distance moduli per walker (``jla_distance_moduli``) instead of C_l.
 ``jla_likelihood_add`` mirrors ``JLALikelihood_Add`` (:221-262).
 
+``JLAMargeLikelihood`` is the same dataset with ``JLA_marginalize = T``
+(``cmbl_open`` tag ``"JLA_MARGE"``): alpha and beta are integrated over the
+reference's fixed grid (:235-252, 1207-1217) inside the likelihood, which then
+has no nuisance parameters.  ``jla_marge_grid`` and ``jla_marge_loglike_host``
+restate the grid and the integral on the host.
+
 ``jla_loglike_host`` is a float64 numpy restatement of
 ``JLA_alpha_beta_like`` (:1028-1168): the public host reference.  It factors
 V(alpha, beta) and solves for the three right-hand sides instead of forming
@@ -13,6 +19,7 @@ details (the squared errors of the light-curve file and ``zfacsq``).
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 
 import numpy as np
@@ -37,12 +44,12 @@ def _open_as_written(name: str, dataset: str) -> str:
 class JLADataset:
     """read_jla_dataset + jla_prep (:602-760, 874-957) on the host."""
 
-    def __init__(self, dataset: str, overrides: dict | None = None):
+    def __init__(self, dataset: str, overrides: dict | None = None, marginalised: bool = False):
         ini = IniFile(text="".join(f"{k} = {v}\n" for k, v in (overrides or {}).items()))
         ini._open(dataset, 0)          # first definition wins: the overrides
         self.filename = dataset
         self.name = ini.get("name", "")
-        if ini.read_bool("JLA_marginalize"):
+        if ini.read_bool("JLA_marginalize") and not marginalised:    # marginalised: JLAMargeLikelihood's own use
             raise NotImplementedError("JLA_marginalize = T is not supported")
         if ini.read_bool("absdist_file"):
             raise NotImplementedError("absdist_file is not supported")
@@ -187,17 +194,125 @@ class JLALikelihood(NativeCMBLikelihood):
         return self._lc
 
 
-def jla_likelihood_add(like_list, ini: IniFile):
-    """JLALikelihood_Add (:221-262): use_JLA, jla_dataset, jla_version; JLA_marginalize refused."""
+# ------------------------------------------------------------ JLA_marginalize = T
+
+ALPHA_CENTER = float(np.float32(0.14))       # JLA_alpha_center, JLA_beta_center: single-precision
+BETA_CENTER = float(np.float32(3.123))       # literals promoted to double (:119-120)
+MARGE_DEFAULTS = dict(steps=7, width_alpha=0.003, width_beta=0.04)     # :237-239
+
+
+def jla_marge_grid(steps: int = 7, width_alpha: float = 0.003, width_beta: float = 0.04, center=None):
+    """(alpha, beta) of the marginalisation grid in the reference's order
+    (:243-251): alpha_i outer, beta_i inner, alpha_i^2 + beta_i^2 <= steps^2."""
+    ca, cb = (ALPHA_CENTER, BETA_CENTER) if center is None else (float(center[0]), float(center[1]))
+    pts = [(ai, bi) for ai in range(-steps, steps + 1) for bi in range(-steps, steps + 1)
+           if ai * ai + bi * bi <= steps * steps]
+    return (np.array([ca + ai * float(width_alpha) for ai, _ in pts]),
+            np.array([cb + bi * float(width_beta) for _, bi in pts]))
+
+
+def jla_marge_points_host(dataset, mu, steps: int = 7, width_alpha: float = 0.003, width_beta: float = 0.04,
+                          center=None):
+    """JLA_marge_grid (:1209-1213): jla_loglike_host at every grid point, LOGZERO where V does not factor."""
+    D = dataset if isinstance(dataset, JLADataset) else JLADataset(dataset, marginalised=True)
+    al, be = jla_marge_grid(steps, width_alpha, width_beta, center)
+    return np.array([jla_loglike_host(D, a, b, mu) for a, b in zip(al, be)])
+
+
+def jla_marge_loglike_host(dataset, mu, steps: int = 7, width_alpha: float = 0.003, width_beta: float = 0.04,
+                           center=None) -> float:
+    """-lnL of jla_LnLike with JLA_marginalize = T (:1207-1217) for one row of
+    distance moduli, in float64 numpy on top of jla_loglike_host: the points
+    that return LOGZERO are masked out of the minimum and of the sum."""
+    L = jla_marge_points_host(dataset, mu, steps, width_alpha, width_beta, center)
+    L = L[L != LOGZERO]
+    if L.size == 0:
+        raise ValueError("V(alpha, beta) is not positive definite at any grid point")
+    best = L.min()
+    v = best - np.log(np.sum(np.exp(-L + best)) * float(width_alpha) * float(width_beta))
+    return float(v) if np.isfinite(v) else LOGZERO
+
+
+class JLAMargeLikelihood(NativeCMBLikelihood):
+    """The JLA dataset with alpha and beta marginalised on the reference's grid,
+    in the HIP library (tag ``"JLA_MARGE"``).  V(alpha, beta)^-1 of every grid
+    point is formed on the device when the dataset is opened; an evaluation is
+    then one batched quadratic form per grid point.  ``loglike_batch(dl, None)``
+    takes ``dl`` as for JLALikelihood; there are no nuisance parameters."""
+    LikelihoodType = "SN"
+
+    def __init__(self, dataset: str, steps: int = 7, width_alpha: float = 0.003, width_beta: float = 0.04,
+                 overrides: dict | None = None):
+        over = dict(overrides or {})
+        over.update(JLA_marge_steps=int(steps), JLA_step_width_alpha=repr(float(width_alpha)),
+                    JLA_step_width_beta=repr(float(width_beta)))
+        super().__init__("JLA_MARGE", dataset, over)
+        self.name = "JLA"
+        self.tag = ""                      # GetTag falls back to the name: chi2_JLA
+        self.version = JLA_VERSION
+        self.n_theory = N.lib().cmbl_theory_len(self._h)
+        self.dataset = dataset
+        self.steps, self.width_alpha, self.width_beta = int(steps), float(width_alpha), float(width_beta)
+        self._overrides = over
+        self._lc = None
+        ng, npts, nb = C.c_int(), C.c_int(), C.c_size_t()
+        N.check(N.lib().cmbl_jla_marge_info(self._h, C.byref(ng), C.byref(npts), C.byref(nb)), self._h)
+        self._n_grid, self.n_points, self._grid_bytes = ng.value, npts.value, nb.value
+
+    @property
+    def n_grid(self) -> int:
+        """Grid points integrated over: those of the grid at which V(alpha, beta) factors."""
+        return self._n_grid
+
+    @property
+    def grid_bytes(self) -> int:
+        """Device bytes of the stored V(alpha_g, beta_g)^-1 (0 with diag_errors)."""
+        return self._grid_bytes
+
+    @property
+    def lc(self):
+        """zcmb / zhel of the light-curve file, to build theory rows from distances."""
+        if self._lc is None:
+            d = JLADataset(self.dataset, self._overrides, marginalised=True)
+            self._lc = _LightCurves(d.zcmb, d.zhel)
+        return self._lc
+
+    def loglike_batch(self, dl, nuis=None, out=None, workspace=None):
+        import torch
+        if nuis is None:
+            nuis = torch.empty((dl.shape[0], 0), dtype=torch.float64, device=dl.device)
+        return super().loglike_batch(dl, nuis, out, workspace)
+
+    def loglike_batch_sparse(self, dl, nuis, out, count, workspace=None):
+        import torch
+        if nuis is None:
+            nuis = torch.empty((dl.shape[0], 0), dtype=torch.float64, device=dl.device)
+        return super().loglike_batch_sparse(dl, nuis, out, count, workspace)
+
+    def loglike_host(self, dl, nuis=None):
+        dl = np.asarray(dl)
+        return super().loglike_host(dl, np.empty((dl.shape[0], 0)) if nuis is None else nuis)
+
+
+def jla_likelihood_add(like_list, ini: IniFile, allow_marginalize: bool = False):
+    """JLALikelihood_Add (:221-262): use_JLA, jla_dataset, jla_version.  JLA_marginalize = T
+    is refused unless allow_marginalize: then JLA_marge_steps, JLA_step_width_alpha and
+    JLA_step_width_beta are read from the same ini (:237-239) and a JLAMargeLikelihood is added."""
     if not ini.read_bool("use_JLA", False):
         return None
-    if ini.read_bool("JLA_marginalize", False):
+    marge = ini.read_bool("JLA_marginalize", False)
+    if marge and not allow_marginalize:
         raise NotImplementedError("JLA_marginalize = T is not supported: alpha_JLA and beta_JLA are sampled")
     if "jla_dataset" in ini:
         fname = ini.relative_filename("jla_dataset")
     else:
         fname = os.path.join(ini.datasetdir, "jla.dataset")
-    like = JLALikelihood(fname)
+    if marge:
+        like = JLAMargeLikelihood(fname, int(ini.get("JLA_marge_steps", "7")),
+                                  float(ini.get("JLA_step_width_alpha", "0.003")),
+                                  float(ini.get("JLA_step_width_beta", "0.04")))
+    else:
+        like = JLALikelihood(fname)
     like.version = ini.get("jla_version", JLA_VERSION)
     like_list.add(like)
     return like

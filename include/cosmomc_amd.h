@@ -72,7 +72,17 @@ typedef struct cmbl cmbl_t;
  * covariance components, file names as written or relative to the dataset;
  * nuisance parameters alpha_JLA beta_JLA; JLA_marginalize = T and absdist_file
  * are CMBL_ERR_UNSUPPORTED, a matrix of the wrong size or a set number outside
- * 0..9 CMBL_ERR_FORMAT), "WMAP" CMBL_ERR_UNSUPPORTED (external library), any other tag a CMBlikes
+ * 0..9 CMBL_ERR_FORMAT), "JLA_MARGE" the same dataset with JLA_marginalize = T
+ * (supernovae_JLA.f90:235-252, 1207-1217): alpha and beta integrated over the
+ * reference's fixed grid, options JLA_marge_steps (7; outside 0..16 is
+ * CMBL_ERR_ARG), JLA_step_width_alpha (0.003) and JLA_step_width_beta (0.04; a
+ * width <= 0 is CMBL_ERR_ARG) from the dataset or the overrides; no nuisance
+ * parameters; V(alpha, beta)^-1 of every grid point is formed on the device at
+ * open (cmbl_jla_marge_info); a point where V does not factor is dropped as the
+ * reference drops it, none left or the two-scriptm assumption violated at a
+ * point is CMBL_ERR_FORMAT (JLA_alpha_center and JLA_beta_center move the
+ * grid's centre from the reference's constants: an extension, for tests),
+ * "WMAP" CMBL_ERR_UNSUPPORTED (external library), any other tag a CMBlikes
  * dataset (CMBlikes.f90; like_approx HL or gaussian, binned, or exact,
  * unbinned: ExactChiSq CMBlikes.f90:967-979, up to 4 maps).
  * override_ini: "key = value" lines applied over the dataset file, as
@@ -96,6 +106,12 @@ int  cmbl_info(const cmbl_t *h, int *n_nuis, int *cl_lmax, int *speed,
  * likelihoods.  A calculator serves such a row with n_fields = 1, fields = {0},
  * lmax = len - 1. */
 int  cmbl_theory_len(const cmbl_t *h);
+
+/* "JLA_MARGE": n_grid the (alpha, beta) grid points the likelihood integrates
+ * over (those the reference keeps), n_points the grid's points, grid_bytes the
+ * device memory of their inverse covariance matrices (0 with diag_errors).
+ * Any pointer may be NULL.  CMBL_ERR_ARG for another likelihood. */
+int  cmbl_jla_marge_info(const cmbl_t *h, int *n_grid, int *n_points, size_t *grid_bytes);
 
 /* Derived parameters a likelihood outputs per sample (the '*' names of its
  * nuisance .paramnames): their count and space-separated names (pointer owned

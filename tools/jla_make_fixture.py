@@ -9,6 +9,17 @@
 archive is made and packed on its own, so one can be added without touching
 the other.
 
+--archive marge (tests/golden/jla/jla_marge.tar.xz) holds the goldens of the
+alpha, beta-marginalised likelihood (JLA_marginalize = T): per case the option
+lines and the reference's jla_LnLike at the five mu rows of a dataset of the
+first archive, which it names and does not repeat.  --out DIR extracts those
+datasets from the committed first archive where DIR lacks them, and writes per
+case DIR/marge/<case>/options.txt and the reference's main ini
+DIR/<dataset>/<case>.ini; tools/jla_marge_ref_harness (see its header), run in
+DIR/<dataset> on that ini, writes DIR/marge/<case>/ref.txt.  syn5_indef_s2 has
+widths that put a grid point near (0.2, 2.5), where that dataset's V is
+indefinite: the reference drops it and keeps the rest.
+
 Seeded (np.random.RandomState, whose stream is frozen) synthetic datasets: SN
 rows taken from the JLA light-curve file, component matrices cut from one
 jointly positive-semidefinite 3n x 3n matrix with blocks scaled by
@@ -42,6 +53,14 @@ DATASETS = [("syn37", 37, tuple(BLOCK), True, 3701),
             ("syn5_indef", 5, ("mag", "mag_stretch"), False, 501)]
 UPPER = [("syn21_upper", 21, ("mag", "stretch", "mag_colour"), False, 2101)]
 ARCHIVES = {"fixture": ("jla_fixture.tar.xz", DATASETS), "upper": ("jla_upper.tar.xz", UPPER)}
+#        case             dataset       steps  width_alpha  width_beta
+MARGE = [("syn37_s7", "syn37", 7, 0.003, 0.04),
+         ("syn37_s0", "syn37", 0, 0.003, 0.04),
+         ("syn70_s2", "syn70", 2, 0.003, 0.04),
+         ("syn131_s1", "syn131", 1, 0.003, 0.04),
+         ("syn37_diag_s7", "syn37_diag", 7, 0.003, 0.04),
+         ("syn5_indef_s2", "syn5_indef", 2, 0.06, 0.623)]
+MARGE_ARCHIVE = "jla_marge.tar.xz"
 FILES = ["jla.dataset", "lc.txt", "cases.txt", "ref.txt"] + [k + ".dat" for k in BLOCK]
 
 
@@ -118,20 +137,45 @@ def make(name, n, comps, two, seed, src, out):
             f.write(" ".join(g9(x) for x in mu) + "\n")
 
 
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "jla")
+
+
+def make_marge(out):
+    import lzma
+    if not all(os.path.exists(os.path.join(out, ds, "jla.dataset")) for _, ds, *_ in MARGE):
+        with open(os.path.join(GOLDEN_DIR, ARCHIVES["fixture"][0]), "rb") as f:
+            tar = tarfile.open(fileobj=io.BytesIO(lzma.decompress(f.read())))
+            for m in tar.getmembers():              # jla/<name>/<file> -> out/<name>/<file>
+                m.name = m.name.split("/", 1)[1]
+                tar.extract(m, out)
+    for case, ds, steps, wa, wb in MARGE:
+        opts = "JLA_marge_steps = %d\nJLA_step_width_alpha = %s\nJLA_step_width_beta = %s\n" % (steps, g9(wa), g9(wb))
+        os.makedirs(os.path.join(out, "marge", case), exist_ok=True)
+        with open(os.path.join(out, "marge", case, "options.txt"), "w") as f:
+            f.write("dataset = %s\n" % ds + opts)
+        with open(os.path.join(out, ds, case + ".ini"), "w") as f:
+            f.write("use_JLA = T\nJLA_marginalize = T\njla_dataset = jla.dataset\n" + opts)
+        print("wrote", os.path.join(out, "marge", case))
+
+
 def pack(root, archive="fixture"):
-    fname, datasets = ARCHIVES[archive]
-    dst = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "jla")
+    if archive == "marge":
+        datasets, files, top = [(os.path.join("marge", c),) for c, *_ in MARGE], ["options.txt", "ref.txt"], "jla_"
+        fname = MARGE_ARCHIVE
+    else:
+        (fname, datasets), files, top = ARCHIVES[archive], FILES, "jla/"
+    dst = GOLDEN_DIR
     os.makedirs(dst, exist_ok=True)
     buf = io.BytesIO()
     with tarfile.open(fileobj=buf, mode="w:xz", preset=9) as tar:
         for name, *_ in datasets:
-            for fn in FILES:
+            for fn in files:
                 p = os.path.join(root, name, fn)
                 if not os.path.exists(p):
                     if fn == "ref.txt":
                         raise SystemExit("missing %s: run the reference harness first" % p)
                     continue
-                ti = tarfile.TarInfo("jla/%s/%s" % (name, fn))
+                ti = tarfile.TarInfo("%s%s/%s" % (top, name, fn))
                 data = open(p, "rb").read()
                 ti.size, ti.mtime, ti.mode = len(data), 0, 0o644
                 tar.addfile(ti, io.BytesIO(data))
@@ -145,10 +189,12 @@ def main():
     ap.add_argument("--lcparams")
     ap.add_argument("--out")
     ap.add_argument("--pack")
-    ap.add_argument("--archive", choices=sorted(ARCHIVES), default="fixture")
+    ap.add_argument("--archive", choices=sorted(ARCHIVES) + ["marge"], default="fixture")
     a = ap.parse_args()
     if a.pack:
         return pack(a.pack, a.archive)
+    if a.archive == "marge":
+        return make_marge(a.out)
     src = [l for l in open(a.lcparams) if not l.lstrip().startswith("#")]
     for name, n, comps, two, seed in ARCHIVES[a.archive][1]:
         make(name, n, comps, two, seed, src, os.path.join(a.out, name))
