@@ -8,6 +8,7 @@
 #include "jlamarge.h"
 #include "sampler.h"
 #include "theorycalc.h"
+#include "wl.h"
 
 namespace cmamd {
 void sampler_create(cmbs *s, const cmbs_config_t *cfg);
@@ -104,6 +105,7 @@ int cmbl_open(const char *tag, const char *dataset_path, const char *override_in
         else if (t == "SPTPOL_TEEE" || t == "SPTPOL_BB") h->like = cmamd::make_sptpol(ini, t);   // CMB.f90:86-91
         else if (t == "JLA") h->like = cmamd::make_jla(ini);   // JLALikelihood_Add (supernovae_JLA.f90:221-262)
         else if (t == "JLA_MARGE") h->like = cmamd::make_jla_marge(ini);   // the same with JLA_marginalize = T (:235-252)
+        else if (t == "WL") h->like = cmamd::make_wl(ini);   // WLLikelihood_Add (wl.f90:72-102)
         else if (t == "WMAP")   // CMB.f90:75-84: needs the external WMAP likelihood library
             cmamd::fail(CMBL_ERR_UNSUPPORTED, "cmbl_open: dataset tag '%s' not supported", tag);
         else h->like = cmamd::make_cmblikes(ini, t);      // TCMBLikes, TBK_planck (BKPLANCK), TSmica_planck (SMICA)
@@ -133,6 +135,16 @@ int cmbl_theory_len(const cmbl_t *h) { return h && h->like ? h->like->theory_len
 
 int cmbl_jla_marge_info(const cmbl_t *h, int *n_grid, int *n_points, size_t *grid_bytes) {
     if (!h || !h->like || !cmamd::jla_marge_info(h->like.get(), n_grid, n_points, grid_bytes)) return CMBL_ERR_ARG;
+    return CMBL_OK;
+}
+
+int cmbl_wl_info(const cmbl_t *h, int *dims) {
+    if (!h || !h->like || !cmamd::wl_info(h->like.get(), dims)) return CMBL_ERR_ARG;
+    return CMBL_OK;
+}
+
+int cmbl_wl_arrays(const cmbl_t *h, int *ls_cl, double *ls_bessel, int *used_items) {
+    if (!h || !h->like || !cmamd::wl_arrays(h->like.get(), ls_cl, ls_bessel, used_items)) return CMBL_ERR_ARG;
     return CMBL_OK;
 }
 

@@ -152,6 +152,11 @@ class Ini {
     void open(const std::string &filename);
     void override_text(const char *text);          // "key = value" lines
     bool has(const std::string &key) const { return kv_.count(key) != 0; }
+    std::vector<std::string> keys() const {
+        std::vector<std::string> k;
+        for (const auto &kv : kv_) k.push_back(kv.first);
+        return k;
+    }
     std::string str(const std::string &key, const std::string &def = "") const;
     std::string str_required(const std::string &key) const;
     std::string relative_filename(const std::string &key, bool required) const;
@@ -387,6 +392,7 @@ std::unique_ptr<Like> make_cmblikes(const Ini &ini, const std::string &tag);
 std::unique_ptr<Like> make_sptpol(const Ini &ini, const std::string &tag);   // SPTPOL_TEEE / SPTPOL_BB
 std::unique_ptr<Like> make_jla(const Ini &ini);                             // jla.hip
 std::unique_ptr<Like> make_jla_marge(const Ini &ini);                       // jlamarge.hip
+std::unique_ptr<Like> make_wl(const Ini &ini);                              // wl.hip
 
 }  // namespace cmamd
 

@@ -82,6 +82,8 @@ typedef struct cmbl cmbl_t;
  * reference drops it, none left or the two-scriptm assumption violated at a
  * point is CMBL_ERR_FORMAT (JLA_alpha_center and JLA_beta_center move the
  * grid's centre from the reference's constants: an extension, for tests),
+ * "WL" a DES-format weak-lensing and galaxy-clustering dataset (wl.f90; see
+ * cmbl_wl_info below for its theory row and options),
  * "WMAP" CMBL_ERR_UNSUPPORTED (external library), any other tag a CMBlikes
  * dataset (CMBlikes.f90; like_approx HL or gaussian, binned, or exact,
  * unbinned: ExactChiSq CMBlikes.f90:967-979, up to 4 maps).
@@ -106,6 +108,29 @@ int  cmbl_info(const cmbl_t *h, int *n_nuis, int *cl_lmax, int *speed,
  * likelihoods.  A calculator serves such a row with n_fields = 1, fields = {0},
  * lmax = len - 1. */
 int  cmbl_theory_len(const cmbl_t *h);
+
+/* "WL" (the DES-format weak-lensing and galaxy-clustering likelihood, wl.f90):
+ * a walker's theory row is
+ *     [h, omm, chis[nz], Hs[nz], D_growth[nz], P[nl][nz]]
+ * (2 + 3 nz + nl nz doubles): h = H0/100, omm = omdm + omb, chis the comoving
+ * distances and Hs the H(z) of the calculator at z_p (nz = num_z_p: the n(z)
+ * file's rows + 2), D_growth = sqrt(P_lin(0.01, z_p) / P_lin(0.01, 0)), and
+ * P[l * nz + j] the power calc_theory holds in `powers` (wl.f90:549-569) at
+ * kh = (ls_cl[l] + 1/2) / (chis[j] h), z_p[j], 0 where kh is outside the
+ * spectrum's range; nl = size(ls_cl).  The library uses the row as given.
+ * Nuisance parameters in DataParams order (b, m, A, alpha, z0, DzL, DzS), named
+ * by the dataset's nuisance_params file; option keys acc, lmax, ah_factor (read,
+ * not applied), intrinsic_alignment_model = none | DES1YR, used_data_types,
+ * num_gal_bins = 0, and wl_use_weyl as an override key (with gammat or wtheta
+ * wanted: CMBL_ERR_UNSUPPORTED, as wl.f90:201-203).  Any key WL_ReadIni does
+ * not read, and any measurements_format but DES, is CMBL_ERR_UNSUPPORTED and
+ * named in the message.
+ * cmbl_wl_info: dims[8] = nz, nl, size(ls_bessel), Limber columns, num_used,
+ * first_theta_bin_used, num_z_bins, num_gal_bins.  cmbl_wl_arrays: ls_cl [nl],
+ * ls_bessel, used_items [num_used][4] (type index, bin1, bin2, theta bin; all
+ * 1-based); any pointer may be NULL.  CMBL_ERR_ARG for another likelihood. */
+int  cmbl_wl_info(const cmbl_t *h, int *dims);
+int  cmbl_wl_arrays(const cmbl_t *h, int *ls_cl, double *ls_bessel, int *used_items);
 
 /* "JLA_MARGE": n_grid the (alpha, beta) grid points the likelihood integrates
  * over (those the reference keeps), n_points the grid's points, grid_bytes the
