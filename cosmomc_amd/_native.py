@@ -62,6 +62,14 @@ class CmbgConfig(C.Structure):
                 ("invcov", C.POINTER(C.c_double))]
 
 
+class CmbgTableConfig(C.Structure):
+    _fields_ = [("form", C.c_int), ("coef", C.POINTER(C.c_double)),
+                ("n", C.c_int), ("scale", C.c_double), ("x_min", C.c_double), ("x_max", C.c_double),
+                ("step", C.c_double), ("table", C.POINTER(C.c_double)),
+                ("np", C.c_int), ("perp", C.POINTER(C.c_double)), ("plel", C.POINTER(C.c_double)),
+                ("prob", C.POINTER(C.c_double)), ("DA_rd_fid", C.c_double), ("Hrd_fid", C.c_double)]
+
+
 _lib = None
 
 # cmbs_theory_fn: int (*)(void *user, int W, const double *P_end, long long ld, void *stream)
@@ -142,6 +150,7 @@ def lib():
         L.cmbs_set_theory_calculator.argtypes = [vp, vp]
         L.cmbs_set_like_calculator.argtypes = [vp, i, vp]
         L.cmbg_create.argtypes = [vp, C.POINTER(CmbgConfig), C.POINTER(vp), C.c_char_p, sz]
+        L.cmbg_create_table.argtypes = [vp, C.POINTER(CmbgTableConfig), C.POINTER(vp), C.c_char_p, sz]
         L.cmbg_destroy.argtypes = [vp]
         L.cmbg_last_error.argtypes = [vp]
         L.cmbg_last_error.restype = C.c_char_p

@@ -473,6 +473,23 @@ int cmbg_create(cmbt_t *calc, const cmbg_config_t *cfg, cmbg_t **out, char *errb
     return CMBL_OK;
 }
 
+int cmbg_create_table(cmbt_t *calc, const cmbg_table_config_t *cfg, cmbg_t **out, char *errbuf, size_t errlen) {
+    std::string err;
+    if (!calc || !cfg || !out) {
+        put_err(errbuf, errlen, "cmbg_create_table: null argument");
+        return CMBL_ERR_ARG;
+    }
+    *out = nullptr;
+    std::unique_ptr<cmbg> g(new cmbg);
+    int rc = guarded(&err, [&] { cmamd::theorytable_create(g.get(), calc, cfg); });
+    if (rc) {
+        put_err(errbuf, errlen, err.c_str());
+        return rc;
+    }
+    *out = g.release();
+    return CMBL_OK;
+}
+
 void cmbg_destroy(cmbg_t *g) { delete g; }
 const char *cmbg_last_error(const cmbg_t *g) { return g ? g->last_error.c_str() : ""; }
 

@@ -42,19 +42,29 @@ struct cmbt {
     cmamd::DevBuf dcoef, dlim;
 };
 
-// Gaussian likelihood on derived quantities (cmbg_*): n scalar surfaces over
-// the calculator's monomials with coefficient columns of its own
+// Likelihood on derived quantities (cmbg_*): n scalar surfaces over the
+// calculator's monomials with coefficient columns of its own.  form 0: the
+// Gaussian (cmbg_create); CMBG_TABLE_1D / CMBG_TABLE_2D: a tabulated
+// likelihood on 1 / 2 surfaces (cmbg_create_table)
 struct cmbg {
     cmbt *calc = nullptr;         // not owned
-    int n = 0;
+    int n = 0, form = 0;
     std::string last_error;
     // device tables: dcoef [Kp][TD_ND] as cmbt's, obs [TD_ND] (padded with
     // zeros), invcov [n][n]
     cmamd::DevBuf dcoef, obs, invcov;
+    // tabulated forms.  1-D: table [tn] and p = scale, x_min, x_max, step.
+    // 2-D: table = perp [tn], plel [tn], prob [tn][tn] (perp outer) and p =
+    // DA_rd_fid, Hrd_fid, d_perp, d_plel, perp[0], perp[tn - 2], plel[0],
+    // plel[tn - 2]
+    int tn = 0;
+    double p[8] = {};
+    cmamd::DevBuf table;
 };
 
 namespace cmamd {
 void theorygauss_create(cmbg *g, cmbt *calc, const cmbg_config_t *cfg);
+void theorytable_create(cmbg *g, cmbt *calc, const cmbg_table_config_t *cfg);
 void theorygauss_eval(cmbg *g, int M, const double *P, long long ld, int num_params, double *out, int *fail_flags,
                       hipStream_t stream);
 void theorycalc_create(cmbt *t, const cmbt_config_t *cfg);

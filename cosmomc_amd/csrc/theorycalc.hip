@@ -17,6 +17,9 @@
 //
 // Gaussian likelihoods on such surfaces (cmbg_*, theory_gauss_kernel): the
 // same accumulators, then (v - obs)^T invcov (v - obs) / 2 per point.
+//
+// Tabulated likelihoods on 1 or 2 such surfaces (cmbg_create_table,
+// theory_table_kernel in theorytable.h): a table lookup with a hard edge.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -301,6 +304,12 @@ __global__ __launch_bounds__(TD_THREADS) void theory_gauss_kernel(TheoryGaussArg
     if (a.fail) a.fail[m] = bad;
 }
 
+}  // namespace cmamd
+
+#include "theorytable.h"
+
+namespace cmamd {
+
 static size_t tc_lds_bytes(int Kp) { return ((size_t)Kp * TC_TW + (size_t)TC_KC * TC_TN) * 8; }
 static size_t td_lds_bytes(int n_in) { return (size_t)n_in * TD_TM * 8; }
 
@@ -499,6 +508,95 @@ void theorygauss_create(cmbg *g, cmbt *calc, const cmbg_config_t *c) {
     upload(g->invcov, std::vector<double>(c->invcov, c->invcov + (size_t)n * n));
 }
 
+// the cell index the kernels form at the upper end of an axis:
+// floor((hi - lo) / d), the largest any point inside [lo, hi] gets (the
+// subtraction, the division and floor are monotone)
+static double table_top_cell(double lo, double hi, double d) { return std::floor((hi - lo) / d); }
+
+void theorytable_create(cmbg *g, cmbt *calc, const cmbg_table_config_t *c) {
+    if (c->form != CMBG_TABLE_1D && c->form != CMBG_TABLE_2D)
+        fail(CMBL_ERR_ARG, "cmbg_create_table: form must be CMBG_TABLE_1D or CMBG_TABLE_2D");
+    if (!c->coef) fail(CMBL_ERR_ARG, "cmbg_create_table: null coefficient table");
+    const int ns = c->form == CMBG_TABLE_1D ? 1 : 2;
+    std::vector<double> tab;
+    if (c->form == CMBG_TABLE_1D) {
+        if (!c->table) fail(CMBL_ERR_ARG, "cmbg_create_table: null table");
+        if (c->n < 2) fail(CMBL_ERR_ARG, "cmbg_create_table: n must be at least 2");
+        if (!std::isfinite(c->scale) || c->scale == 0.0) fail(CMBL_ERR_ARG, "cmbg_create_table: scale must be finite and not 0");
+        if (!std::isfinite(c->x_min) || !std::isfinite(c->x_max) || !(c->x_min < c->x_max))
+            fail(CMBL_ERR_ARG, "cmbg_create_table: x_min must be below x_max, both finite");
+        if (!std::isfinite(c->step) || !(c->step > 0.0)) fail(CMBL_ERR_ARG, "cmbg_create_table: step must be positive");
+        for (int i = 0; i < c->n; i++)
+            if (!std::isfinite(c->table[i])) fail(CMBL_ERR_ARG, "cmbg_create_table: table entry %d is not finite", i);
+        const double top = table_top_cell(c->x_min, c->x_max, c->step);
+        if (!(top + 1 < (double)c->n))
+            fail(CMBL_ERR_ARG, "cmbg_create_table: at x_max the cell is %.0f, and its upper entry lies beyond the %d of the table",
+                 top, c->n);
+        tab.assign(c->table, c->table + c->n);
+        g->tn = c->n;
+        const double p[8] = {c->scale, c->x_min, c->x_max, c->step, 0, 0, 0, 0};
+        std::copy(p, p + 8, g->p);
+    } else {
+        if (!c->perp || !c->plel || !c->prob) fail(CMBL_ERR_ARG, "cmbg_create_table: null table");
+        const int np = c->np;
+        if (np < 3 || np > 32768) fail(CMBL_ERR_ARG, "cmbg_create_table: np must be in 3..32768");
+        if (!std::isfinite(c->DA_rd_fid) || c->DA_rd_fid == 0.0 || !std::isfinite(c->Hrd_fid) || c->Hrd_fid == 0.0)
+            fail(CMBL_ERR_ARG, "cmbg_create_table: DA_rd_fid and Hrd_fid must be finite and not 0");
+        for (int i = 0; i < np; i++)
+            if (!std::isfinite(c->perp[i]) || !std::isfinite(c->plel[i]))
+                fail(CMBL_ERR_ARG, "cmbg_create_table: knot %d is not finite", i);
+        for (size_t i = 0; i < (size_t)np * np; i++)
+            if (!std::isfinite(c->prob[i])) fail(CMBL_ERR_ARG, "cmbg_create_table: prob entry %zu is not finite", i);
+        const double *axis[2] = {c->perp, c->plel};
+        double d[2];
+        for (int x = 0; x < 2; x++) {
+            d[x] = axis[x][1] - axis[x][0];
+            if (!(d[x] > 0.0)) fail(CMBL_ERR_ARG, "cmbg_create_table: axis %d has knot[1] - knot[0] <= 0", x);
+            const double top = table_top_cell(axis[x][0], axis[x][np - 2], d[x]);
+            if (!(top + 1 < (double)np))
+                fail(CMBL_ERR_ARG, "cmbg_create_table: axis %d: at knot[np - 2] the cell is %.0f, beyond the grid", x, top);
+        }
+        tab.reserve(2 * (size_t)np + (size_t)np * np);
+        tab.insert(tab.end(), c->perp, c->perp + np);
+        tab.insert(tab.end(), c->plel, c->plel + np);
+        tab.insert(tab.end(), c->prob, c->prob + (size_t)np * np);
+        g->tn = np;
+        const double p[8] = {c->DA_rd_fid, c->Hrd_fid, d[0], d[1], c->perp[0], c->perp[np - 2], c->plel[0], c->plel[np - 2]};
+        std::copy(p, p + 8, g->p);
+    }
+    std::vector<double> coef((size_t)calc->Kp * TD_ND, 0.0);
+    for (int k = 0; k < calc->K; k++) {
+        for (int s = 0; s < ns; s++)
+            if (!std::isfinite(c->coef[(size_t)k * ns + s]))
+                fail(CMBL_ERR_ARG, "cmbg_create_table: coefficient %d, %d is not finite", k, s);
+        std::copy(c->coef + (size_t)k * ns, c->coef + (size_t)(k + 1) * ns, coef.begin() + (size_t)k * TD_ND);
+    }
+    g->calc = calc;
+    g->n = ns;
+    g->form = c->form;
+    upload(g->dcoef, coef);
+    upload(g->table, tab);
+}
+
+static void theorytable_eval(cmbg *g, int M, const double *P, long long ld, double *out, int *fail_flags,
+                             hipStream_t stream) {
+    cmbt *t = g->calc;
+    TheoryTableArgs a{};
+    a.b = basis_args(t, M, P, ld);
+    a.dcoef = g->dcoef.as<double>();
+    a.table = g->table.as<double>();
+    a.form = g->form;
+    a.tn = g->tn;
+    std::copy(g->p, g->p + 8, a.p);
+    a.out = out;
+    a.fail = fail_flags;
+    timed_launch("theory_table_kernel", stream, [&](hipEvent_t e0, hipEvent_t e1) {
+        hipExtLaunchKernelGGL(theory_table_kernel, dim3((M + TD_TM - 1) / TD_TM), dim3(TD_THREADS),
+                              td_lds_bytes(t->n_in), stream, e0, e1, 0, a);
+    });
+    HIP_CHECK(hipGetLastError());
+}
+
 void theorygauss_eval(cmbg *g, int M, const double *P, long long ld, int num_params, double *out, int *fail_flags,
                       hipStream_t stream) {
     cmbt *t = g->calc;
@@ -508,6 +606,10 @@ void theorygauss_eval(cmbg *g, int M, const double *P, long long ld, int num_par
     if (ld < M) fail(CMBL_ERR_ARG, "cmbg_eval: ld %lld below M %d", ld, M);
     for (int p : t->pidx)
         if (p > num_params) fail(CMBL_ERR_ARG, "cmbg_eval: param_index %d outside 1..%d", p, num_params);
+    if (g->form != 0) {
+        theorytable_eval(g, M, P, ld, out, fail_flags, stream);
+        return;
+    }
     TheoryGaussArgs a{};
     a.b = basis_args(t, M, P, ld);
     a.dcoef = g->dcoef.as<double>();

@@ -102,7 +102,8 @@ class BatchedMCMC:
                                                 dl.stride(0)))
 
     def add_derived_likelihood(self, g):
-        """g: cosmomc_amd.derivedlike.DerivedGaussian on the calculator given to
+        """g: cosmomc_amd.derivedlike.DerivedGaussian or DerivedTable (a
+        tabulated likelihood: MGS, the DR1x grids) on the calculator given to
         set_theory_calculator (cmbs_add_derived_likelihood): one more term row
         after the data likelihoods', so every add_likelihood call comes first.
         The row is evaluated at the start point and at every slow trial and

@@ -478,6 +478,71 @@ typedef struct {
  * object.  CMBL_ERR_ARG for n outside 1..32, a NULL table, a non-finite obs or
  * invcov entry, or invcov[i][j] != invcov[j][i]. */
 int  cmbg_create(cmbt_t *calc, const cmbg_config_t *cfg, cmbg_t **out, char *errbuf, size_t errlen);
+
+/* Tabulated likelihoods on 1 or 2 such surfaces: the reference's BAO
+ * likelihoods that are no Gaussians.  The object is a cmbg_t: cmbg_eval (one
+ * launch of theory_table_kernel), cmbg_destroy, cmbg_last_error and
+ * cmbs_add_derived_likelihood take it unchanged.  v_i is formed as above, so it
+ * has cmbt_derived_eval's bits; every division below is an IEEE division, every
+ * operation one rounding in the order written (no fma), as the reference
+ * compiled without fast-math computes them.  r_drag enters the surfaces bare:
+ * rs_rescale is not applied (get_rs_drag is called bare in both forms).
+ *
+ * CMBG_TABLE_1D (BAO_MGS_loglike, bao.f90:390-410), surface 0 = D_V / r_drag:
+ *   alpha  = v_0 / scale                    scale = DVfid / rsfid, a double
+ *   alpha > x_max or alpha < x_min:         out[m] = CMBL_LOGZERO
+ *   ii     = floor((alpha - x_min) / step)  zero-based; step is the reference's
+ *                                           default-real 0.001 as a double,
+ *                                           (double)0.001f, not 0.001
+ *   chi2   = (table[ii] + table[ii + 1]) / 2
+ *   out[m] = chi2 / 2
+ *
+ * CMBG_TABLE_2D (BAO_DR1x_loglike, bao.f90:346-376), surface 0 = D_A / r_drag,
+ * surface 1 = Hofz_Hunit * r_drag:
+ *   a_perp = v_0 / DA_rd_fid
+ *   a_plel = Hrd_fid / v_1                  v_1 = 0 gives +-inf: outside
+ *   a_perp outside [perp[0], perp[np - 2]] or a_plel outside [plel[0],
+ *   plel[np - 2]]:                          out[m] = CMBL_LOGZERO (the upper
+ *                                           bound is the second-to-last knot)
+ *   ii     = floor((a_perp - perp[0]) / (perp[1] - perp[0]))     zero-based,
+ *   jj     = floor((a_plel - plel[0]) / (plel[1] - plel[0]))     no search
+ *   prob   = (1 / ((perp[ii+1] - perp[ii]) * (plel[jj+1] - plel[jj]))) *
+ *            (((prob[ii][jj]     * (perp[ii+1] - a_perp) * (plel[jj+1] - a_plel)
+ *             - prob[ii+1][jj]   * (perp[ii]   - a_perp) * (plel[jj+1] - a_plel))
+ *             - prob[ii][jj+1]   * (perp[ii+1] - a_perp) * (plel[jj]   - a_plel))
+ *             + prob[ii+1][jj+1] * (perp[ii]   - a_perp) * (plel[jj]   - a_plel))
+ *            each product left to right
+ *   out[m] = prob > 0 ? -log(prob) : CMBL_LOGZERO
+ *
+ * Both: a NaN alpha compares false in the reference's bounds test; here it is
+ * CMBL_LOGZERO.  A point outside the calculator's box (a NaN input included)
+ * has out[m] = CMBL_LOGZERO and fail[m] = 1, as in cmbg_eval.  A point's bits
+ * depend on neither M, its place in the batch nor ld. */
+#define CMBG_TABLE_1D 1
+#define CMBG_TABLE_2D 2
+typedef struct {
+    int form;                 /* CMBG_TABLE_1D or CMBG_TABLE_2D */
+    const double *coef;       /* host [n_terms][1] (1-D) or [n_terms][2] (2-D): the surfaces */
+    /* CMBG_TABLE_1D */
+    int n;                    /* table entries, >= 2 */
+    double scale, x_min, x_max, step;
+    const double *table;      /* n */
+    /* CMBG_TABLE_2D */
+    int np;                   /* knots per axis (alpha_npoints), >= 3 */
+    const double *perp;       /* np */
+    const double *plel;       /* np */
+    const double *prob;       /* [np][np], perp the outer index, already divided by its maximum */
+    double DA_rd_fid, Hrd_fid;
+} cmbg_table_config_t;
+/* Copies the tables.  `calc` is not owned and must outlive the object.
+ * CMBL_ERR_ARG for another form, a NULL table, a non-finite table entry, knot,
+ * coefficient or parameter, scale or a fiducial 0, n < 2, np < 3, step <= 0,
+ * x_min >= x_max, knot[1] - knot[0] <= 0 on either axis, and a table too short
+ * for the cell the arithmetic above names at the upper bound: floor((x_max -
+ * x_min) / step) + 1 >= n, or floor((knot[np - 2] - knot[0]) / (knot[1] -
+ * knot[0])) + 1 >= np on either axis (computed on the host in the same
+ * arithmetic; a point inside the bounds cannot get a larger index). */
+int  cmbg_create_table(cmbt_t *calc, const cmbg_table_config_t *cfg, cmbg_t **out, char *errbuf, size_t errlen);
 void cmbg_destroy(cmbg_t *g);
 const char *cmbg_last_error(const cmbg_t *g);
 /* One launch (theory_gauss_kernel), asynchronous on `stream`, for M points:
