@@ -111,6 +111,8 @@ def lib():
         L.cmbl_jla_marge_info.argtypes = [vp, C.POINTER(i), C.POINTER(i), C.POINTER(sz)]
         L.cmbl_wl_info.argtypes = [vp, C.POINTER(i)]
         L.cmbl_wl_arrays.argtypes = [vp, C.POINTER(i), C.POINTER(d), C.POINTER(i)]
+        L.cmbl_sz_info.argtypes = [vp, C.POINTER(i)]
+        L.cmbl_sz_arrays.argtypes = [vp, C.POINTER(d), C.POINTER(d), C.POINTER(i), C.POINTER(i)]
         L.cmbl_derived_info.argtypes = [vp, C.POINTER(i), C.POINTER(C.c_char_p)]
         L.cmbl_derived_batch.argtypes = [vp, i, vp, ll, vp, ll, vp]
         L.cmbl_workspace_size.argtypes = [vp, i]

@@ -8,6 +8,7 @@
 #include "jlamarge.h"
 #include "sampler.h"
 #include "theorycalc.h"
+#include "sz.h"
 #include "wl.h"
 
 namespace cmamd {
@@ -106,6 +107,7 @@ int cmbl_open(const char *tag, const char *dataset_path, const char *override_in
         else if (t == "JLA") h->like = cmamd::make_jla(ini);   // JLALikelihood_Add (supernovae_JLA.f90:221-262)
         else if (t == "JLA_MARGE") h->like = cmamd::make_jla_marge(ini);   // the same with JLA_marginalize = T (:235-252)
         else if (t == "WL") h->like = cmamd::make_wl(ini);   // WLLikelihood_Add (wl.f90:72-102)
+        else if (t == "SZ") h->like = cmamd::make_sz(ini);   // SZLikelihood_Add (szcounts.f90:1385-1499)
         else if (t == "WMAP")   // CMB.f90:75-84: needs the external WMAP likelihood library
             cmamd::fail(CMBL_ERR_UNSUPPORTED, "cmbl_open: dataset tag '%s' not supported", tag);
         else h->like = cmamd::make_cmblikes(ini, t);      // TCMBLikes, TBK_planck (BKPLANCK), TSmica_planck (SMICA)
@@ -145,6 +147,16 @@ int cmbl_wl_info(const cmbl_t *h, int *dims) {
 
 int cmbl_wl_arrays(const cmbl_t *h, int *ls_cl, double *ls_bessel, int *used_items) {
     if (!h || !h->like || !cmamd::wl_arrays(h->like.get(), ls_cl, ls_bessel, used_items)) return CMBL_ERR_ARG;
+    return CMBL_OK;
+}
+
+int cmbl_sz_info(const cmbl_t *h, int *dims) {
+    if (!h || !h->like || !cmamd::sz_info(h->like.get(), dims)) return CMBL_ERR_ARG;
+    return CMBL_OK;
+}
+
+int cmbl_sz_arrays(const cmbl_t *h, double *steps_z, double *dncat, int *j1, int *j2) {
+    if (!h || !h->like || !cmamd::sz_arrays(h->like.get(), steps_z, dncat, j1, j2)) return CMBL_ERR_ARG;
     return CMBL_OK;
 }
 

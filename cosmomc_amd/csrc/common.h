@@ -393,6 +393,7 @@ std::unique_ptr<Like> make_sptpol(const Ini &ini, const std::string &tag);   // 
 std::unique_ptr<Like> make_jla(const Ini &ini);                             // jla.hip
 std::unique_ptr<Like> make_jla_marge(const Ini &ini);                       // jlamarge.hip
 std::unique_ptr<Like> make_wl(const Ini &ini);                              // wl.hip
+std::unique_ptr<Like> make_sz(const Ini &ini);                              // sz.hip
 
 }  // namespace cmamd
 

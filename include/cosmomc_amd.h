@@ -84,6 +84,8 @@ typedef struct cmbl cmbl_t;
  * grid's centre from the reference's constants: an extension, for tests),
  * "WL" a DES-format weak-lensing and galaxy-clustering dataset (wl.f90; see
  * cmbl_wl_info below for its theory row and options),
+ * "SZ" the Planck SZ cluster counts (szcounts.f90; see cmbl_sz_info below for
+ * its ini, theory row and options),
  * "WMAP" CMBL_ERR_UNSUPPORTED (external library), any other tag a CMBlikes
  * dataset (CMBlikes.f90; like_approx HL or gaussian, binned, or exact,
  * unbinned: ExactChiSq CMBlikes.f90:967-979, up to 4 maps).
@@ -131,6 +133,31 @@ int  cmbl_theory_len(const cmbl_t *h);
  * 1-based); any pointer may be NULL.  CMBL_ERR_ARG for another likelihood. */
 int  cmbl_wl_info(const cmbl_t *h, int *dims);
 int  cmbl_wl_arrays(const cmbl_t *h, int *ls_cl, double *ls_bessel, int *used_items);
+
+/* "SZ" (the Planck SZ cluster-counts likelihood, szcounts.f90, its 2D form
+ * N(z, q)): the file opened is a small ini with cat_file, thetas_file,
+ * skyfracs_file and ylims_file (the reference's data/SZ_*.txt, relative to the
+ * ini), optionally nuisance_params (a .paramnames of five names; default
+ * alpha_SZ ystar_SZ bias_SZ scatter_SZ beta_SZ) and the option keys of the
+ * reference's run ini: 2D, prior_alpha_SZ, prior_ystar_SZ, prior_scatter_SZ,
+ * prior_beta_SZ, prior_wtg, prior_lens, prior_cccp, prior_ns, prior_omegabh2.
+ * 1D = T and any other key are CMBL_ERR_UNSUPPORTED, the key named in the
+ * message; a ylims file whose row count is not patches x thetas, and fewer
+ * than two thetas, are CMBL_ERR_FORMAT.  A walker's theory row is
+ *     [H0, ns, ombh2, E[nzs], dA[nzs], grid[nzs][nm]]
+ * (3 + 2 nzs + nzs nm doubles): E = H(z)/H0 and dA the angular diameter
+ * distance in Mpc/h at steps_z, grid[j * nm + m] what get_grid leaves
+ * (dndlnM deg2 dVdzdO, szcounts.f90:1317-1334) at steps_z[j] and mass
+ * exp(31 + 0.05 (m + 1/2)) Msun/h.  The library uses the row as given; which
+ * mass function filled it is the provider's business.  Nuisance parameters
+ * in DataParams order (alpha, log10 ystar, bias, scatter, beta).
+ * cmbl_sz_info: dims[8] = nzs, nm, redshift bins Nz, S/N bins, thetas,
+ * patches, ln Y nodes, catalogue rows kept.  cmbl_sz_arrays: steps_z [nzs],
+ * DNcat [Nz][S/N bins], and the 0-based steps j1[Nz], j2[Nz] between which a
+ * redshift bin is integrated; any pointer may be NULL.  CMBL_ERR_ARG for
+ * another likelihood. */
+int  cmbl_sz_info(const cmbl_t *h, int *dims);
+int  cmbl_sz_arrays(const cmbl_t *h, double *steps_z, double *dncat, int *j1, int *j2);
 
 /* "JLA_MARGE": n_grid the (alpha, beta) grid points the likelihood integrates
  * over (those the reference keeps), n_points the grid's points, grid_bytes the
