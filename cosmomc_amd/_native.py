@@ -113,6 +113,8 @@ def lib():
         L.cmbl_wl_arrays.argtypes = [vp, C.POINTER(i), C.POINTER(d), C.POINTER(i)]
         L.cmbl_sz_info.argtypes = [vp, C.POINTER(i)]
         L.cmbl_sz_arrays.argtypes = [vp, C.POINTER(d), C.POINTER(d), C.POINTER(i), C.POINTER(i)]
+        L.cmbl_mpk_info.argtypes = [vp, C.POINTER(i)]
+        L.cmbl_mpk_arrays.argtypes = [vp, C.POINTER(d), C.POINTER(d), C.POINTER(d)]
         L.cmbl_derived_info.argtypes = [vp, C.POINTER(i), C.POINTER(C.c_char_p)]
         L.cmbl_derived_batch.argtypes = [vp, i, vp, ll, vp, ll, vp]
         L.cmbl_workspace_size.argtypes = [vp, i]

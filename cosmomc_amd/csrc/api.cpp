@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "jlamarge.h"
+#include "mpk.h"
 #include "sampler.h"
 #include "theorycalc.h"
 #include "sz.h"
@@ -108,6 +109,8 @@ int cmbl_open(const char *tag, const char *dataset_path, const char *override_in
         else if (t == "JLA_MARGE") h->like = cmamd::make_jla_marge(ini);   // the same with JLA_marginalize = T (:235-252)
         else if (t == "WL") h->like = cmamd::make_wl(ini);   // WLLikelihood_Add (wl.f90:72-102)
         else if (t == "SZ") h->like = cmamd::make_sz(ini);   // SZLikelihood_Add (szcounts.f90:1385-1499)
+        else if (t == "MPK") h->like = cmamd::make_mpk(ini, false);       // MPKLikelihood_Add (mpk.f90:90-115)
+        else if (t == "WIGGLEZ") h->like = cmamd::make_mpk(ini, true);    // WiggleZLikelihood_Add (wigglez.f90:170-200)
         else if (t == "WMAP")   // CMB.f90:75-84: needs the external WMAP likelihood library
             cmamd::fail(CMBL_ERR_UNSUPPORTED, "cmbl_open: dataset tag '%s' not supported", tag);
         else h->like = cmamd::make_cmblikes(ini, t);      // TCMBLikes, TBK_planck (BKPLANCK), TSmica_planck (SMICA)
@@ -157,6 +160,16 @@ int cmbl_sz_info(const cmbl_t *h, int *dims) {
 
 int cmbl_sz_arrays(const cmbl_t *h, double *steps_z, double *dncat, int *j1, int *j2) {
     if (!h || !h->like || !cmamd::sz_arrays(h->like.get(), steps_z, dncat, j1, j2)) return CMBL_ERR_ARG;
+    return CMBL_OK;
+}
+
+int cmbl_mpk_info(const cmbl_t *h, int *dims) {
+    if (!h || !h->like || !cmamd::mpk_info(h->like.get(), dims)) return CMBL_ERR_ARG;
+    return CMBL_OK;
+}
+
+int cmbl_mpk_arrays(const cmbl_t *h, double *k, double *data, double *invcov) {
+    if (!h || !h->like || !cmamd::mpk_arrays(h->like.get(), k, data, invcov)) return CMBL_ERR_ARG;
     return CMBL_OK;
 }
 

@@ -394,6 +394,7 @@ std::unique_ptr<Like> make_jla(const Ini &ini);                             // j
 std::unique_ptr<Like> make_jla_marge(const Ini &ini);                       // jlamarge.hip
 std::unique_ptr<Like> make_wl(const Ini &ini);                              // wl.hip
 std::unique_ptr<Like> make_sz(const Ini &ini);                              // sz.hip
+std::unique_ptr<Like> make_mpk(const Ini &ini, bool wigglez);               // mpk.hip (tags MPK, WIGGLEZ)
 
 }  // namespace cmamd
 

@@ -86,6 +86,10 @@ typedef struct cmbl cmbl_t;
  * cmbl_wl_info below for its theory row and options),
  * "SZ" the Planck SZ cluster counts (szcounts.f90; see cmbl_sz_info below for
  * its ini, theory row and options),
+ * "MPK" a galaxy power-spectrum dataset of mpk.f90's format (sdss_lrgDR4.dataset)
+ * and "WIGGLEZ" one redshift bin of wigglez.f90 (wigglez_nov11a.dataset, the
+ * keys of the wigglez_common_dataset file as overrides; see cmbl_mpk_info below
+ * for the theory row, the keys and the refusals),
  * "WMAP" CMBL_ERR_UNSUPPORTED (external library), any other tag a CMBlikes
  * dataset (CMBlikes.f90; like_approx HL or gaussian, binned, or exact,
  * unbinned: ExactChiSq CMBlikes.f90:967-979, up to 4 maps).
@@ -158,6 +162,47 @@ int  cmbl_wl_arrays(const cmbl_t *h, int *ls_cl, double *ls_bessel, int *used_it
  * another likelihood. */
 int  cmbl_sz_info(const cmbl_t *h, int *dims);
 int  cmbl_sz_arrays(const cmbl_t *h, double *steps_z, double *dncat, int *j1, int *j2);
+
+/* "MPK" (mpk.f90) and "WIGGLEZ" (wigglez.f90): the galaxy power-spectrum
+ * likelihoods, bias and Q marginalised inside as the reference does; no
+ * nuisance parameters, cl_lmax all zero.  A walker's theory row is
+ *     [a_scl, kh_min, P[nk]]
+ * (2 + nk doubles, nk the kbands used): a_scl = DV_fid / (H0 D_V(z)), exactly 1
+ * without use_scaling (compute_scaling_factor, mpk.f90:46-56); kh_min =
+ * exp(PK%x(1)), the lower edge of the provider's k grid; P[i] =
+ * PowerAt(max(kh_min, a_scl k_i), z) as the provider's interpolator returns it,
+ * before the division by a_scl^3 and the GiggleZ factor.  The library forms
+ * k_scaled = max(kh_min, a_scl k_i) again from the row and does the rest of
+ * MPK_LnLike (:312-407) / WiggleZ_LnLike (:545-641), single-precision normV, Q
+ * and minchisq and the running normV of WiggleZ included.
+ * "MPK" keys (MPK_ReadIni :117-244): name, num_mpk_points_full,
+ * num_mpk_kbands_full, min/max_mpk_points_use, min/max_mpk_kbands_use,
+ * kbands_file, measurements_file, windows_file, cov_file (its selected block is
+ * inverted once on the host), use_scaling with DV_fid (missing:
+ * CMBL_ERR_FORMAT), redshift (0.35), Q_marge, Q_flat, Q_mid, Q_sigma, Ag (1.4),
+ * and the override key mpk_dataset_nonlinear, which only says which P(k) the
+ * provider is to use.  "WIGGLEZ" keys (TWiggleZCommon_ReadIni and
+ * WiggleZ_ReadIni :203-437): those, the seven Use_*-hr_region switches (none
+ * set: CMBL_ERR_FORMAT), redshift (within 0.001 of 0.22, 0.41, 0.6 or 0.78),
+ * Use_gigglez (without nonlinear_wigglez = T: CMBL_ERR_FORMAT),
+ * nonlinear_wigglez, num_conflicts, type_conflict1, name_conflict1 (read, not
+ * acted on), and gigglez_dir, the directory of
+ * gigglezfiducialmodel_matterpower_{a..d}.dat (default: the dataset's; an
+ * extension, the reference uses its global data directory).  Any other key,
+ * name = twodf and name = lrg_2009 are CMBL_ERR_UNSUPPORTED; more than 64
+ * points used is CMBL_ERR_UNSUPPORTED.
+ * Where the reference stops the program the walker's -lnL is CMBL_LOGZERO, for
+ * that walker alone: a row entry that is NaN or Inf, a_scl <= 0, a k_scaled
+ * outside the GiggleZ spline's knots, a 2 x 2 matrix of the Q_flat branch that
+ * is not positive definite, normV <= 0, and a value that is not finite.
+ * cmbl_mpk_info: dims[8] = points used, kbands used, regions used, zbin (0 for
+ * "MPK"), Q mode (0 Q_marge = F, 1 Q_flat, 2 the Gaussian Q grid, 3 Q_sigma =
+ * 0), has_cov, use_scaling, use_gigglez.  cmbl_mpk_arrays: the selected k [nk],
+ * the data vector [regions][np] and the inverse covariance [regions][np][np]
+ * (without a cov_file the diagonal matrix of 1 / sdev^2); any pointer may be
+ * NULL.  CMBL_ERR_ARG for another likelihood. */
+int  cmbl_mpk_info(const cmbl_t *h, int *dims);
+int  cmbl_mpk_arrays(const cmbl_t *h, double *k, double *data, double *invcov);
 
 /* "JLA_MARGE": n_grid the (alpha, beta) grid points the likelihood integrates
  * over (those the reference keeps), n_points the grid's points, grid_bytes the
