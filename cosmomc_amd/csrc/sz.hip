@@ -97,6 +97,15 @@ SzData load_sz(const Ini &ini) {
     d.nthetas = (int)d.thetas.size(), d.npatches = (int)d.skyfracs.size();
     if (d.nthetas < 2) fail(CMBL_ERR_FORMAT, "SZ: thetas_file holds %d thetas, fewer than two", d.nthetas);
     if (d.npatches < 1) fail(CMBL_ERR_FORMAT, "SZ: skyfracs_file holds no patch");
+    // The neighbour of the nearest theta on thp's side (:1020-1027) lies outside the reference's table when the
+    // nearest is the first entry and larger than thp, or the last and smaller: only a first entry that is the
+    // least and a last that is the greatest rule that out for every thp.  The order in between is free.
+    for (int t = 0; t < d.nthetas; t++)
+        if (d.thetas[t] < d.thetas[0] || d.thetas[t] > d.thetas[d.nthetas - 1])
+            fail(CMBL_ERR_UNSUPPORTED,
+                 "SZ: thetas_file must begin with its least theta and end with its greatest (entry %d is %g, the first "
+                 "%g, the last %g): the reference reads outside its table otherwise",
+                 t + 1, d.thetas[t], d.thetas[0], d.thetas[d.nthetas - 1]);
     const std::vector<double> yl = sz_column(ini, "ylims_file");
     if (yl.size() != (size_t)d.npatches * d.nthetas)
         fail(CMBL_ERR_FORMAT, "SZ: ylims_file holds %zu rows, expected %d patches x %d thetas", yl.size(), d.npatches,
@@ -262,7 +271,8 @@ struct SzPoint {
 // The theta bracket (:1010-1028): the nearest theta (the first of two equally
 // near) and its neighbour on thp's side, or the end pair beyond either end.
 // thp equal to the last theta would make the reference read one theta past its
-// table with weight (thp - th1) = 0; l2 stays inside.
+// table with weight (thp - th1) = 0; l2 stays inside.  The thetas need not
+// ascend, but the first is the least and the last the greatest (load_sz).
 __device__ __forceinline__ void sz_bracket(const SzDev &d, SzPoint &p) {
     const int nth = d.nthetas;
     if (p.thp > d.theta_max) p.l1 = nth - 1, p.l2 = nth - 2;
@@ -287,7 +297,8 @@ __device__ __forceinline__ void sz_bracket(const SzDev &d, SzPoint &p) {
         p.l1 = best;
         p.l2 = d.thetas[best] > p.thp ? best - 1 : best + 1;
         if (p.l2 >= nth) p.l2 = nth - 2;
-        if (p.l2 < 0) p.l2 = 1;
+        // l2 >= 0: best == 0 with thetas[0] > thp >= theta_min needs a first theta that is not the least, which
+        // load_sz refuses; a NaN thp compares false and takes best + 1
     }
 }
 
@@ -553,6 +564,10 @@ struct SzLike : Like {
         HIP_CHECK(hipDeviceSynchronize());
     }
 
+    // The workspace is the completeness table of min(W, SZ_MAXW) walkers and nothing else: float32
+    // comp[w][q][j * nm + m], q the S/N bin (SZ_NQ = 5), j the step in z (nzs), m the step in ln M (nm), so
+    // 5 * nzs * nm * 4 bytes a walker.  After a call it holds the walkers of the last chunk, slot w0 + w at w
+    // (INTEGRATION.md states the same; tests/test_gpu_sz_edges.py reads it).
     size_t ws_floats() const { return (size_t)SZ_NQ * dev.npts; }
     size_t workspace_size(int W) const override {
         if (W <= 0) return 0;

@@ -136,6 +136,11 @@ class SZDataset:
         nth, npatch = len(self.thetas), len(self.skyfracs)
         if nth < 2:
             raise SZFormatError("SZ: fewer than two thetas")
+        # the bracket's second theta (:1020-1027) is outside the reference's table when the nearest theta is the
+        # first entry and larger than thp, or the last and smaller: the order in between is free
+        if self.thetas[0] > self.thetas.min() or self.thetas[-1] < self.thetas.max():
+            raise NotImplementedError("SZ: thetas_file must begin with its least theta and end with its greatest: "
+                                      "the reference reads outside its table otherwise")
         if len(yl) != nth * npatch:
             raise SZFormatError("SZ: ylims has %d rows, expected %d" % (len(yl), nth * npatch))
         self.ylims = yl.reshape(nth, npatch).T.copy()                 # [patch][theta]; patch runs fastest in the file
@@ -340,11 +345,14 @@ def sz_completeness(ds: SZDataset, row, nuis, dtype=np.float64):
     return comp.astype(T)
 
 
-def sz_counts(ds: SZDataset, row, nuis, dtype=np.float64):
-    """DN[Nz][nq] of integrate_m_zq (:827-869): one running sum, z outer."""
+def sz_counts(ds: SZDataset, row, nuis, dtype=np.float64, comp=None):
+    """DN[Nz][nq] of integrate_m_zq (:827-869): one running sum, z outer.
+    ``comp``: sz_completeness of these arguments when the caller has it (it
+    does not depend on the row's grid block)."""
     T = np.dtype(dtype).type
     nzs, nm = ds.nzs, ds.nm
-    comp = sz_completeness(ds, row, nuis, dtype)
+    if comp is None:
+        comp = sz_completeness(ds, row, nuis, dtype)
     grid = np.asarray(row)[3 + 2 * nzs:3 + 2 * nzs + nzs * nm].astype(T).reshape(nzs, nm)
     sz = ds.steps_z.astype(T)
     DN = np.zeros((ds.Nz, ds.nq), dtype=T)

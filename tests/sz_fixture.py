@@ -2,8 +2,8 @@
 (tests/golden/sz/sz_fixture.tar.xz: inputs from tools/sz_make_fixture.py, which
 calls make_synthetic below; outputs from tools/sz_ref_harness.f90).
 
-A synthetic dataset is seeded: 3-8 sky patches whose fractions sum to about
-0.65, 4-6 filter sizes theta, noise levels ylims[patch][theta] rising with
+A synthetic dataset is seeded: 1-8 sky patches whose fractions sum to about
+0.65, 2-6 filter sizes theta (ascending, but for syn_unsorted), noise levels ylims[patch][theta] rising with
 theta, and a catalogue of (z, z error, S/N) rows.  The grid of the model
 (steps in z and ln M, the S/N bins, the ln Y integration) is the reference's
 own and is in the code, not in the data, so a small dataset runs every path
@@ -31,17 +31,87 @@ CENTRE = (1.789, -0.186, 0.8, 0.075, 2.0 / 3.0)                  # batch2/SZ_plu
 THETA_INSIDE = (2.0, 40.0)
 THETA_CONTAINS = (0.3, 1e10)
 
+# syn_unsorted: the file's thetas are these positions of the ascending list.  The least stays first and the
+# greatest last (the reference reads outside its table otherwise, and the loaders refuse such a file); the inner
+# three are out of order, so the nearest theta is found by the linear search
+UNSORTED_ORDER = (0, 3, 1, 2, 4)
+
 #            name            keyword arguments of make_synthetic
 GOLDENS = [("syn_inside", dict(seed=201, npatch=5, ntheta=6, theta=THETA_INSIDE, priors=("prior_scatter_SZ", "prior_ystar_SZ"),
                                points="all")),
            ("syn_contains", dict(seed=202, npatch=8, ntheta=5, theta=THETA_CONTAINS, points="all")),
            ("syn_cat", dict(seed=203, npatch=3, ntheta=4, theta=THETA_INSIDE, cat="edges", points="few")),
-           ("syn_lastrow", dict(seed=204, npatch=3, ntheta=4, theta=THETA_INSIDE, cat="lastrow", points="few"))] + \
+           ("syn_lastrow", dict(seed=204, npatch=3, ntheta=4, theta=THETA_INSIDE, cat="lastrow", points="few")),
+           ("syn_two", dict(seed=206, npatch=1, ntheta=2, theta=THETA_INSIDE, points="few")),
+           ("syn_unsorted", dict(seed=207, npatch=3, ntheta=5, theta=THETA_INSIDE, points="few", order=UNSORTED_ORDER))] + \
           [("syn_" + p, dict(seed=205, npatch=3, ntheta=4, theta=THETA_INSIDE, priors=(p,), points="prior")) for p in PRIORS] + \
           [("syn_prior_all", dict(seed=205, npatch=3, ntheta=4, theta=THETA_INSIDE, priors=tuple(PRIORS), points="prior"))]
 WATSON_STRIDE = 37                     # sz/watson/row_sample.txt keeps every 37th number of the Watson row
 SYNTHETIC = [n for n, _ in GOLDENS]
 NAMES = SYNTHETIC + ["real"]          # the real SZ_* data files with a few points (tools/sz_make_fixture.py --real)
+
+
+# ---- the pointwise tests of the completeness table (test_gpu_sz_edges.py; measured in test_szcounts.py)
+
+def _with(**kw):
+    p = dict(zip(PARAM_NAMES, CENTRE))
+    p.update({k + "_SZ": v for k, v in kw.items()})
+    return tuple(p[n] for n in PARAM_NAMES)
+
+
+ZERO_SCATTER = (1.789, -0.186, 0.8, 0.0, 2.0 / 3.0)               # the scatter_SZ = 0 point of "few" and "all"
+# dataset -> the nuisance points whose tables are compared entry by entry.  On syn_inside the scatters are
+# chosen by the window of ln Y nodes they give (window_classes below)
+EDGE_CASES = {"syn_inside": [CENTRE, _with(scatter=1e-3), _with(scatter=0.5), _with(scatter=3.0), _with(scatter=-0.075),
+                             ZERO_SCATTER, _with(scatter=0.0, beta=0.3)],
+              "syn_two": [CENTRE, ZERO_SCATTER],
+              "syn_unsorted": [CENTRE, ZERO_SCATTER]}
+# the points at which test_szcounts.py measures f64 against long double entry by entry, a dataset at a time: the
+# cases above but -0.075 (it gives +0.075's table), 0.5 (2.2e-16, measured once) and the second scatter_SZ = 0
+# point of syn_inside; and the worse of the two ill-conditioned goldens (alpha_SZ = 1, bias_SZ = 0.1,
+# scatter_SZ = 0.022).  COMP_LD_ABS is what it measures, the largest absolute difference of an entry: 2^-47
+# (7.105e-15) and 2^-44 (5.684e-14), each a single-precision ulp of a small entry whose rounding tipped
+LD_TABLE_CASES = {"syn_inside": [CENTRE, _with(scatter=1e-3), _with(scatter=3.0), ZERO_SCATTER,
+                                 (1.0, -0.186, 0.1, 0.022, 2.0 / 3.0)],
+                  "syn_two": [CENTRE, ZERO_SCATTER], "syn_unsorted": [CENTRE, ZERO_SCATTER]}
+COMP_LD_ABS = {"syn_inside": 7.11e-15, "syn_two": 7.11e-15, "syn_unsorted": 5.69e-14}
+WINDOW_CLASSES = ("below", "cut_low", "inside", "cut_high", "above", "wider")
+
+
+def scaling(ds, row, nuis):
+    """theta500 and y500 [nzs][nm] of a theory row and nuisance point (:221-243), in f64."""
+    from cosmomc_amd import szcounts as S
+    row = np.asarray(row, dtype=np.float64)
+    alpha, logystar, bias, _, beta = (float(x) for x in nuis)
+    H0, E, dA = row[0], row[3:3 + ds.nzs], row[3 + ds.nzs:3 + 2 * ds.nzs]
+    mfac = np.exp(ds.steps_m) * bias / S.M_PIVOT * (100 / H0)
+    dfac = (100 * dA / 500 / H0)[:, None]
+    thp = S.THETASTAR * (H0 / 70) ** S.M2_3 * mfac[None, :] ** S.ALPHA_THETA * (E ** S.M2_3)[:, None] / dfac
+    ystar = 10.0 ** logystar / 2.0 ** alpha * S.YSTAR_NORM
+    yp = ystar * (H0 / 70) ** (-2 + alpha) * mfac[None, :] ** alpha * (E ** beta)[:, None] / (dfac * dfac)
+    return thp, yp
+
+
+def window_classes(ds, row, nuis):
+    """How many (z, m) have their window of ln Y nodes, |lny - ln y500| <= sqrt(746) sqrt(2) |scatter_SZ|,
+    wholly below the grid of nodes, cut at its lower end, inside it, cut at its upper end, wholly above it,
+    or wider than all of it; and how many of those below leave sz_compl_kernel's loop without a node (the
+    window's upper end two steps or more under the first node)."""
+    from cosmomc_amd import szcounts as S
+    mu = np.log(scaling(ds, row, nuis)[1])
+    reach = np.sqrt(746.0) * S.SQRT2 * abs(float(nuis[3]))
+    lo, hi, first, last = mu - reach, mu + reach, ds.lny[0], ds.lny[-1]
+    n = {"below": hi < first, "above": lo > last, "wider": (lo < first) & (hi > last),
+         "cut_low": (lo < first) & (hi >= first) & (hi <= last), "cut_high": (lo >= first) & (lo <= last) & (hi > last),
+         "inside": (lo >= first) & (hi <= last), "empty": hi <= first - 2 * S.DLNY}
+    assert sum(np.count_nonzero(n[c]) for c in WINDOW_CLASSES) == mu.size
+    return {c: int(np.count_nonzero(v)) for c, v in n.items()}
+
+
+def ulp_apart(a, b):
+    """Where two float32 arrays of finite numbers of one sign are neighbouring floats."""
+    ia, ib = (np.ascontiguousarray(x, dtype=np.float32).view(np.int32).astype(np.int64) for x in (a, b))
+    return np.abs(ia - ib) == 1
 
 
 def analytic_sigma(R):
@@ -117,24 +187,28 @@ def write_cases(d, pts):
         f.write("".join(" ".join("%.17g" % x for x in p) + "\n" for p in pts))
 
 
-def make_synthetic(d, seed, npatch, ntheta, theta, cat="plain", priors=(), points="all"):
+def make_synthetic(d, seed, npatch, ntheta, theta, cat="plain", priors=(), points="all", order=None):
     """Write a dataset under d: data/SZ_*.txt and data/SZ.paramnames as the
     reference opens them, the project's sz.ini, the reference's run ini
-    sz_ref.ini, and cases.txt; returns the nuisance points."""
+    sz_ref.ini, and cases.txt; returns the nuisance points.  ``order``: the
+    positions of the ascending thetas in file order (default: ascending); the
+    rows of ylims follow their thetas."""
     rng = np.random.RandomState(seed)
     dd = os.path.join(d, "data")
     os.makedirs(dd, exist_ok=True)
     th = np.exp(np.linspace(np.log(theta[0]), np.log(theta[1]), ntheta))
+    order = list(range(ntheta)) if order is None else list(order)
+    assert sorted(order) == list(range(ntheta))
     with open(os.path.join(dd, "SZ_thetas.txt"), "w") as f:
-        f.write("".join("%.6e\n" % t for t in th))
+        f.write("".join("%.6e\n" % th[k] for k in order))
     sky = rng.uniform(0.5, 1.5, npatch)
     sky = 0.65 * sky / sky.sum()
     with open(os.path.join(dd, "SZ_skyfracs.txt"), "w") as f:
         f.write("".join("%.6e\n" % s for s in sky))
+    yl = [["%.5e\n" % (6e-5 * (1 + 0.5 * i / npatch) * (1 + 0.1 * rng.uniform()) * (1 + t) ** 0.7) for i in range(npatch)]
+          for t in th]                                               # drawn in ascending order of theta
     with open(os.path.join(dd, "SZ_ylims.txt"), "w") as f:        # patch fastest
-        for t in th:
-            for i in range(npatch):
-                f.write("%.5e\n" % (6e-5 * (1 + 0.5 * i / npatch) * (1 + 0.1 * rng.uniform()) * (1 + t) ** 0.7))
+        f.write("".join("".join(yl[k]) for k in order))
     with open(os.path.join(dd, "SZ_cat.txt"), "w") as f:
         f.write("".join("%12.6f %12.5f %12.5f\n" % r for r in catalogue(rng, cat)))
     with open(os.path.join(dd, "SZ.paramnames"), "w") as f:

@@ -19,6 +19,9 @@ Tolerance inputs of the GPU tests, measured here on the goldens (absolute, on
     from 1 - erf in its cancellation range, where f64 keeps no relative
     accuracy, and those bins hold clusters), 1.5e-10 at most elsewhere.  The
     test below measures the two worst points, the centre and the largest -lnL.
+(c) for test_gpu_sz_edges.py, per entry of the completeness table: f64 against
+    long double, 7.1e-15 on syn_inside and syn_two, 5.7e-14 on syn_unsorted
+    (test_completeness_f64_against_long_double says where).
 """
 import ctypes as C
 import filecmp
@@ -126,11 +129,13 @@ def test_longdouble_restatement(goldens, datasets):
 
 
 def test_goldens_cover_the_branches(goldens, datasets):
-    """Both extrapolating theta branches and the bracket run in syn_inside, the
-    bracket alone in syn_contains; completeness clips at fsky at the least
+    """Both extrapolating theta branches and the bracket run in syn_inside, in
+    syn_two (two thetas, one patch: the least the loaders accept) and in
+    syn_unsorted, the bracket alone in syn_contains; completeness clips at fsky at the least
     scatter; scatter_SZ = 0 and beta_SZ != 2/3 are there; the catalogue of
     syn_cat has a bin above 10, empty bins and rescaled (non-integer) columns."""
-    for name, lo, hi in (("syn_inside", True, True), ("syn_contains", False, False)):
+    for name, lo, hi in (("syn_inside", True, True), ("syn_contains", False, False), ("syn_two", True, True),
+                         ("syn_unsorted", True, True)):
         g, ds = goldens[name], datasets[name]
         row = g.row
         E, dA = row[3:3 + ds.nzs], row[3 + ds.nzs:3 + 2 * ds.nzs]
@@ -151,6 +156,70 @@ def test_goldens_cover_the_branches(goldens, datasets):
     assert np.any(cat[:, 2] < 6) and np.any((cat[:, 0] == -1) & (cat[:, 2] > 40)) and np.any((cat[:, 0] == -1) & (cat[:, 2] < 8))
     last = np.loadtxt(os.path.join(goldens["syn_lastrow"].dir, "data", "SZ_cat.txt"))
     assert last[-1, 2] >= 6 and datasets["syn_lastrow"].DNcat.sum() == np.count_nonzero(last[:, 2] >= 6) + 1
+
+
+def test_smallest_and_unsorted_goldens(goldens, datasets):
+    """syn_two is the least the loaders accept; in syn_unsorted every theta is the nearest of some theta500
+    inside the range, each inner one from either side, so the scan over unsorted thetas meets them all."""
+    two, uns = datasets["syn_two"], datasets["syn_unsorted"]
+    assert len(two.thetas) == 2 and len(two.skyfracs) == 1 and two.ylims.shape == (1, 2)
+    assert len(uns.thetas) == 5 and len(uns.skyfracs) == 3
+    for name in ("syn_two", "syn_unsorted"):
+        assert [tuple(p) for p in goldens[name].points[[0, 2]]] == [sf.CENTRE, sf.ZERO_SCATTER]
+    thp = sf.scaling(uns, goldens["syn_unsorted"].row, sf.CENTRE)[0]
+    ins = (thp >= uns.thetas.min()) & (thp <= uns.thetas.max())
+    near = np.argmin(np.abs(uns.thetas[None, None, :] - thp[:, :, None]), axis=2)
+    for t in range(5):
+        assert np.any(ins & (near == t))
+    for t in (1, 2, 3):
+        assert np.any(ins & (near == t) & (uns.thetas[t] > thp)) and np.any(ins & (near == t) & (uns.thetas[t] < thp))
+
+
+def test_window_classes_of_the_edge_cases(goldens, datasets):
+    """The six kinds of ln Y node window sz_compl_kernel can meet (sf.window_classes) all occur over the
+    syn_inside cases of test_gpu_sz_edges.py, and the loop without a node does.  Counted: scatter_SZ = 0.075:
+    7033 cut low, 26530 inside, 37 cut high, 120 above; 1e-3: 963 below (876 without a node), 72 cut low, 32565
+    inside, 120 above; 0.5: 28658 wider, 4924 cut low, 112 cut high, 26 above; 3.0: all 33720 wider."""
+    g, ds = goldens["syn_inside"], datasets["syn_inside"]
+    total = dict.fromkeys(sf.WINDOW_CLASSES + ("empty",), 0)
+    for nu in sf.EDGE_CASES["syn_inside"]:
+        if nu[3] != 0:
+            n = sf.window_classes(ds, g.row, nu)
+            print(nu[3], n)
+            for c in total:
+                total[c] += n[c]
+    assert all(v > 0 for v in total.values()), total
+    assert sf.window_classes(ds, g.row, sf.EDGE_CASES["syn_inside"][3])["wider"] == ds.nzs * ds.nm
+
+
+@pytest.mark.parametrize("name", sorted(sf.LD_TABLE_CASES))
+def test_completeness_f64_against_long_double(goldens, datasets, name):
+    """(c) The bound of test_gpu_sz_edges.py, entry by entry: sz_completeness in f64 against long double over
+    sf.LD_TABLE_CASES, both rounded to single precision as the reference's table is.  Measured, the largest
+    absolute difference: syn_inside 7.1e-15 (scatter_SZ = 1e-3 and the ill-conditioned golden; 8.9e-16 at the
+    centre, 3.6e-15 at scatter_SZ = 0, 0 at 3.0; 2.2e-16 at 0.5, measured once and not repeated here), syn_two
+    7.1e-15, syn_unsorted 5.7e-14 (its scatter_SZ = 0 table; 3.6e-15 at the centre).  Each of these is one
+    single-precision ulp of a small entry (2^-47 for one of 7.9e-8, 2^-44 below 9.5e-7): the rounding to single
+    tipped.  Thousands of smaller entries differ by more than an ulp and less than that absolutely: they are
+    1 - erf in its cancellation range, where f64 keeps no relative accuracy.  No entry is non-finite, and on
+    the host scatter_SZ = -0.075 gives +0.075's table."""
+    g, ds = goldens[name], datasets[name]
+    worst = 0.0
+    for nu in sf.LD_TABLE_CASES[name]:
+        f64 = S.sz_completeness(ds, g.row, nu)
+        ld = S.sz_completeness(ds, g.row, nu, np.longdouble)
+        assert np.all(np.isfinite(f64)) and np.all(np.isfinite(ld))
+        diff = np.abs(f64.astype(np.longdouble) - ld).astype(np.float64)
+        at = diff > 0
+        i = np.unravel_index(np.argmax(diff), diff.shape)
+        print(name, nu, "(c) max |f64 - long double| per entry:", diff.max(), "at an entry of", f64[i], "; entries that differ:",
+              np.count_nonzero(at), "of them neighbouring floats:", np.count_nonzero(sf.ulp_apart(f64, ld.astype(np.float64))),
+              "; the largest entry that differs:", f64[at].max() if at.any() else 0.0)
+        worst = max(worst, float(diff.max()))
+        if name == "syn_inside" and tuple(nu) == sf.CENTRE:
+            assert np.array_equal(S.sz_completeness(ds, g.row, sf.EDGE_CASES["syn_inside"][4]), f64)
+    print(name, "(c) max |f64 - long double| per entry:", worst)
+    assert worst <= sf.COMP_LD_ABS[name]
 
 
 def test_theory_row_matches_harness(extracted, goldens, datasets):
@@ -222,6 +291,43 @@ def test_fewer_than_two_thetas_is_a_format_error(goldens, tmp_path):
     assert rc == FORMAT and "thetas" in msg, (rc, msg)
     with pytest.raises(S.SZFormatError, match="thetas"):
         S.SZDataset(ini)
+
+
+def _reorder_thetas(g, tmp_path, order):
+    """A copy of a dataset with the thetas, and the ylims rows that go with them, in another order."""
+    ini = _copy(g, tmp_path)
+    th = open(tmp_path / "data" / "SZ_thetas.txt").read().split()
+    yl = open(tmp_path / "data" / "SZ_ylims.txt").read().split()
+    npatch = len(yl) // len(th)
+    assert sorted(order) == list(range(len(th))) and npatch * len(th) == len(yl)
+    (tmp_path / "data" / "SZ_thetas.txt").write_text("".join(th[k] + "\n" for k in order))
+    (tmp_path / "data" / "SZ_ylims.txt").write_text("".join(y + "\n" for k in order for y in yl[k * npatch:(k + 1) * npatch]))
+    return ini
+
+
+@pytest.mark.parametrize("order", [(3, 2, 1, 0), (1, 0, 2, 3), (0, 1, 3, 2)],
+                         ids=["descending", "first_not_least", "last_not_greatest"])
+def test_thetas_that_leave_the_reference_table_are_refused(goldens, tmp_path, order):
+    """The reference takes the bracket's second theta from outside its table when the nearest theta is the first
+    entry and larger than theta500, or the last and smaller: no behaviour to follow, so neither loader opens it."""
+    ini = _reorder_thetas(goldens["syn_cat"], tmp_path, order)
+    rc, msg = _open(ini)
+    assert rc == UNSUPPORTED and "thetas_file" in msg and "outside its table" in msg, (rc, msg)
+    with pytest.raises(NotImplementedError, match="thetas_file.*outside its table"):
+        S.SZDataset(ini)
+
+
+def test_unsorted_inner_thetas_open(goldens, datasets, tmp_path):
+    """The order between the least theta, first, and the greatest, last, is free: syn_unsorted opens, and so
+    does syn_cat in that kind of order.  (The library builds its tables on the device when it opens a data set:
+    test_gpu_sz.py opens syn_unsorted there.)"""
+    th = datasets["syn_unsorted"].thetas
+    assert np.array_equal(np.argsort(th), np.argsort(sf.UNSORTED_ORDER)) and len(th) == 5
+    assert th[0] == th.min() and th[-1] == th.max() and np.any(np.diff(th) < 0)
+    ini = _reorder_thetas(goldens["syn_cat"], tmp_path, (0, 2, 1, 3))
+    ds = S.SZDataset(ini)
+    assert np.array_equal(ds.thetas[[0, 2, 1, 3]], datasets["syn_cat"].thetas)
+    assert np.array_equal(ds.ylims[:, [0, 2, 1, 3]], datasets["syn_cat"].ylims)
 
 
 # ---- the ini front end

@@ -10,18 +10,22 @@ The datasets are the seeded synthetic ones of tests/sz_fixture.py (GOLDENS and
 make_synthetic there say what each holds).  --real copies the real SZ_* data
 files, as data, into a dataset "real" with a few points; it is packed when it
 is there.  Every golden has the same cosmology and so the same theory row,
-which --pack keeps once (sz/row.txt) after checking that the copies agree;
+which --pack keeps once (sz/row.txt) after checking that the copies agree
+and that every dataset the archive already holds keeps its inputs and its
+recorded -lnL byte for byte;
 of the row the reference forms with use_watson = T every WATSON_STRIDE-th
 number is kept (sz/watson/row_sample.txt), for sz_theory_row's Watson branch.
 The archive holds text data only.
 """
 import argparse
+import filecmp
 import io
 import os
 import shutil
 import subprocess
 import sys
 import tarfile
+import tempfile
 
 import numpy as np
 
@@ -80,6 +84,16 @@ def main():
         names = [n for n in datasets(base) if n != "watson"]
         rows = [open(os.path.join(base, n, "row.txt")).read() for n in names]
         assert all(r == rows[0] for r in rows), "the goldens' theory rows differ"
+        # a dataset the archive already holds keeps its inputs byte for byte and its recorded -lnL
+        if os.path.exists(sf.GOLDEN):
+            with tempfile.TemporaryDirectory() as old:
+                sf.extract(old, names=[])
+                for n in names:
+                    for f in PACKED:
+                        was = os.path.join(old, "sz", n, f)
+                        if os.path.exists(was):
+                            assert filecmp.cmp(was, os.path.join(base, n, f), shallow=False), \
+                                "%s/%s differs from the archive's" % (n, f)
         buf = io.BytesIO()
 
         def add(path, arc):
